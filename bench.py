@@ -11,20 +11,26 @@ sample with no data-path collective ("weak" scaling, 4096 frames per GPU).
 
 `--gpus N` without a torchrun environment starts the N ranks itself (child processes, one per GPU).
 
-The default run (`python bench.py`, N = 1, mode infer) prints the headline line AND, under "legs", short runs of every
-other BASELINE configuration with the same fields (value, ms_per_step, roofline of the leg's dominant kernel,
+A plain run does only what the headline needs: set-up, `--warmup` untimed steps, `--steps` timed steps, and one JSON
+line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step = wall milliseconds of one timed step, and
+the configuration).  `--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy
+(float32 / float64, 64 MB at most in all; inputs and parameters are seeded, so two builds compare output for output).
+
+`--full` adds everything else the benchmark measures.  With N = 1, mode infer, it also runs, under "legs", short runs
+of every other BASELINE configuration with the same fields (value, ms_per_step, roofline of the leg's dominant kernel,
 cpu_baseline): train B=2048 (x5 steps) and B=8192 (x2, configs[3] per-GPU batch), bf16-storage eval (x10) and bf16
 train B=8192 (x2; configs[2]), tPSFNet train + forward (x20; configs[2]), tactileSRSeqs eval / train (x3; configs[4]
-shape).  `--no-legs` prints the headline only.
+shape).  `--no-legs` skips them.
 
-One JSON line on rank 0 carries the contract fields plus
+With `--full` the JSON line on rank 0 carries the contract fields plus
   roofline     - the dominant kernel (5x5 128->128 conv, 54 % of all FLOPs), timed live
                  with HIP events on the launch stream inside the timed region;
                  `achieved` / `frac` are ALGORITHMIC FLOP/s (direct-conv MACs x 2) against the peak of the
                  pipe the kernel runs on; the executed-product rate (x3 for fp16x3) is `mfma_pipe_util`;
   cpu_baseline - the CPU oracle (a port of the reference's torch CPU path) on the host
                  cores, bounded sample (configs[0]: B=32): the trainer STEP (train_cal_loss + backward +
-                 Adam, cpu/trainer.py:346-362) and the eval forward; rank 0 at N=1 only.
+                 Adam, cpu/trainer.py:346-362) and the eval forward; rank 0 at N=1 only;
+  f32_mfma_path (infer) / forward_only (tpsf) - a second timed run of the other path on the same inputs.
 """
 import argparse
 import json
@@ -42,6 +48,27 @@ C5_FLOP_PER_SAMPLE = 2 * 1600 * 128 * 128 * 25  # one 5x5 128->128 conv launch, 
 PEAK_F32_MFMA = 157.3e12                      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 peak
 PEAK_BF16_MFMA = 2500e12                      # MI355X_MICROARCH.md: dense bf16 MFMA peak
 LAYER_BYTES_PER_SAMPLE = 48.38e6              # SURVEY.md section 8(d), layer-wise fp32 bytes
+DUMP_BYTES = 63_000_000                       # --dump-outputs: array data of all files (< 64 MB with the .npy headers)
+
+
+def dump_outputs(outdir, arrays):
+    """Write {name: tensor} as outdir/<name>.npy: float64 tensors (and integer counters) as float64, the rest as
+    float32.  Past DUMP_BYTES in all, every array keeps the same fraction of its elements, a sample of flat indices
+    drawn from a fixed seed, so two runs of the same shapes sample the same positions."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype in (torch.float64, torch.int64, torch.int32) else t.float()
+        host[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    frac = min(1.0, DUMP_BYTES / total) if total else 1.0
+    for name, a in host.items():
+        if frac < 1.0:
+            idx = np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def make_model(args):
@@ -134,8 +161,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=4096, help="frames per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="headline only (skip the short legs of the other configurations)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-launch roofline, the strict fp32 path, "
+                         "CPU baselines and parity, the tPSFNet forward-only rate, and (N = 1, infer) the legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-legs", action="store_true", help="--full: skip the short legs of the other configurations")
     ap.add_argument("--broadcast-buffers", action="store_true",
                     help="train, N > 1: rank 0's BatchNorm statistics before every forward (torch-DDP default semantics)")
     ap.add_argument("--impl", choices=["fp16x3", "bf16x6", "f32", "bf16x3", "bf16"], default="fp16x3",
@@ -174,8 +206,8 @@ def main():
             dist.init_process_group(backend=backend, init_method="env://")
     run = {"infer": run_infer, "train": run_train, "tpsf": run_tpsf}[args.mode]
     res = run(args, world, rank, dev)
-    if rank == 0 and world == 1 and args.mode == "infer" and not args.no_legs and not args.seqs and not args.impl_given \
-            and args.batch == 4096:
+    if args.full and rank == 0 and world == 1 and args.mode == "infer" and not args.no_legs and not args.seqs \
+            and not args.impl_given and args.batch == 4096:
         res["legs"] = run_legs(args, dev)
     if rank == 0:
         from tactilesr_amd import _lib
@@ -195,7 +227,7 @@ def run_legs(args, dev):
 
     def leg(name, fn, **over):
         a = copy.copy(args)
-        a.seqs, a.impl, a.impl_given, a.batch = False, "fp16x3", False, 4096
+        a.seqs, a.impl, a.impl_given, a.batch, a.dump_outputs = False, "fp16x3", False, 4096, None
         for k, v in over.items():
             setattr(a, k, v)
         t0 = time.perf_counter()
@@ -286,7 +318,7 @@ def run_infer(args, world, rank, dev):
     for _ in range(args.warmup):
         model(LR)
     barrier()
-    model._profile = {}          # HIP-event brackets around every conv launch, keyed (ks, cout)
+    model._profile = {} if args.full else None   # HIP-event brackets around every conv launch, keyed (ks, cout)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         y = model(LR)
@@ -294,6 +326,8 @@ def run_infer(args, world, rank, dev):
     dt = time.perf_counter() - t0
     prof = model._profile
     model._profile = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"output": y})
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -301,7 +335,7 @@ def run_infer(args, world, rank, dev):
 
     # secondary measurement: the strict fp32-MFMA path (v_mfma_f32_32x32x2_f32), 2 steps, same inputs
     f32_ref = None
-    if args.impl != "f32" and not args.seqs and not args.impl_given:
+    if args.full and args.impl != "f32" and not args.seqs and not args.impl_given:
         model.conv_impl = "f32"
         model(LR)
         barrier()
@@ -322,6 +356,25 @@ def run_infer(args, world, rank, dev):
     if rank == 0:
         total = B * world * args.steps
         value = total / dt
+        dtype = {"fp16x3": "f32 as 2 power-of-two-scaled fp16 planes x 3 MFMA products, fp32 accumulate (fp32-grade)",
+                 "bf16x6": "f32 as 3 bf16 planes x 6 MFMA products, fp32 accumulate (fp32-equivalent)",
+                 "f32": "f32", "bf16x3": "bf16x3 (reduced: ~16 significand bits)",
+                 "bf16": "bf16 activation storage + bf16 MFMA operands, fp32 accumulate (reduced precision: 3e-2)"}[args.impl]
+        res = {
+            "metric": "SR samples/sec (4x4->%dx%d)" % (side, side), "value": round(value, 2), "unit": "samples/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+            "config": {"workload": ("tactileSRSeqs (T=8) eval forward 4x4x24->100x100, batch=%d/GPU, fp32 in/out (BASELINE configs[4] shape)" % B)
+                       if args.seqs else
+                       ("tactileSR_model eval forward 4x4->40x40, batch=%d/GPU, fp32 in/out (BASELINE configs[1])" % B),
+                       "batch_per_gpu": B, "scale_factor": model.scale_factor, "seqsCnt": model.seqsCnt,
+                       "parallelism": f"replicas x{world}", "conv_impl": args.impl, "fwd_GFLOP_per_sample": round(fwd_flop / 1e9, 3),
+                       "dist_world_size": dist.get_world_size() if world > 1 else 1,
+                       "dist_backend": ("rccl(nccl)" if dist.get_backend() == "nccl" else dist.get_backend()) if world > 1 else None},
+        }
+        if not args.full:
+            return res
         ev = prof.get((5, 128), [])
         c5_ms = sum(a.elapsed_time(b) for a, b in ev) / max(1, len(ev))
         nprod = {"fp16x3": 3, "bf16x6": 6, "bf16x3": 3, "bf16": 1, "f32": 1}[args.impl]
@@ -340,40 +393,24 @@ def run_infer(args, world, rank, dev):
                       round(sum(a.elapsed_time(b) for a, b in v) / args.steps, 3)
                       for k, v in sorted(prof.items(), key=lambda kv: str(kv[0]))}
         traffic, traffic_src = pmc_traffic(kname, "bf16" if args.impl == "bf16" else "eval") if B == 4096 and not args.seqs else (None, None)
-        dtype = {"fp16x3": "f32 as 2 power-of-two-scaled fp16 planes x 3 MFMA products, fp32 accumulate (fp32-grade)",
-                 "bf16x6": "f32 as 3 bf16 planes x 6 MFMA products, fp32 accumulate (fp32-equivalent)",
-                 "f32": "f32", "bf16x3": "bf16x3 (reduced: ~16 significand bits)",
-                 "bf16": "bf16 activation storage + bf16 MFMA operands, fp32 accumulate (reduced precision: 3e-2)"}[args.impl]
-        res = {
-            "metric": "SR samples/sec (4x4->%dx%d)" % (side, side), "value": round(value, 2), "unit": "samples/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": dtype, "data": "synthetic",
-            "config": {"workload": ("tactileSRSeqs (T=8) eval forward 4x4x24->100x100, batch=%d/GPU, fp32 in/out (BASELINE configs[4] shape)" % B)
-                       if args.seqs else
-                       ("tactileSR_model eval forward 4x4->40x40, batch=%d/GPU, fp32 in/out (BASELINE configs[1])" % B),
-                       "batch_per_gpu": B, "scale_factor": model.scale_factor, "seqsCnt": model.seqsCnt,
-                       "parallelism": f"replicas x{world}", "conv_impl": args.impl, "fwd_GFLOP_per_sample": round(fwd_flop / 1e9, 3),
-                       "dist_world_size": dist.get_world_size() if world > 1 else 1,
-                       "dist_backend": ("rccl(nccl)" if dist.get_backend() == "nccl" else dist.get_backend()) if world > 1 else None},
-            "roofline": {"bound": "mfma", "kernel": kname + ("> (5x5 128->128 conv+BN+ReLU with half of the 1x1 confusion fused, 55% of all FLOPs)"
-                                                             if fused else "> (5x5 128->128 conv+BN+ReLU, 54% of all FLOPs)"),
-                         "achieved": round(alg / 1e12, 2) if alg else None, "peak": peak / 1e12,
-                         "unit": "TFLOP/s", "frac": round(alg / peak, 4) if alg else None,
-                         "algorithmic_flop_per_launch": B * c5_flop,
-                         "mfma_products_per_mac": nprod,
-                         "executed_tflops": round(executed / 1e12, 2) if executed else None,
-                         "mfma_pipe_util": round(executed / peak, 4) if executed else None,
-                         "algorithmic_vs_f32_mfma_peak": round(alg / PEAK_F32_MFMA, 4) if alg else None,
-                         "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": B * (256 * side * side * (2 if args.impl == "bf16" else 4)) + 128 * 128 * 25 * 4,
-                         "avg_launch_ms": round(c5_ms, 3), "launches_timed": len(ev)},
-            "whole_step": {"algorithmic_tflops": round(value / world * fwd_flop / 1e12, 2),
-                           "frac_of_peak": round(value / world * fwd_flop / peak, 4),
-                           "algorithmic_vs_f32_mfma_peak": round(value / world * fwd_flop / PEAK_F32_MFMA, 4),
-                           "layerwise_GBps": None if args.seqs else round(value / world * LAYER_BYTES_PER_SAMPLE / 1e9, 1),
-                           "ms_per_step_by_kernel": per_kernel},
-        }
+        res["roofline"] = {"bound": "mfma",
+                           "kernel": kname + ("> (5x5 128->128 conv+BN+ReLU with half of the 1x1 confusion fused, 55% of all FLOPs)"
+                                             if fused else "> (5x5 128->128 conv+BN+ReLU, 54% of all FLOPs)"),
+                           "achieved": round(alg / 1e12, 2) if alg else None, "peak": peak / 1e12,
+                           "unit": "TFLOP/s", "frac": round(alg / peak, 4) if alg else None,
+                           "algorithmic_flop_per_launch": B * c5_flop,
+                           "mfma_products_per_mac": nprod,
+                           "executed_tflops": round(executed / 1e12, 2) if executed else None,
+                           "mfma_pipe_util": round(executed / peak, 4) if executed else None,
+                           "algorithmic_vs_f32_mfma_peak": round(alg / PEAK_F32_MFMA, 4) if alg else None,
+                           "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
+                           "algorithmic_bytes_per_launch": B * (256 * side * side * (2 if args.impl == "bf16" else 4)) + 128 * 128 * 25 * 4,
+                           "avg_launch_ms": round(c5_ms, 3), "launches_timed": len(ev)}
+        res["whole_step"] = {"algorithmic_tflops": round(value / world * fwd_flop / 1e12, 2),
+                             "frac_of_peak": round(value / world * fwd_flop / peak, 4),
+                             "algorithmic_vs_f32_mfma_peak": round(value / world * fwd_flop / PEAK_F32_MFMA, 4),
+                             "layerwise_GBps": None if args.seqs else round(value / world * LAYER_BYTES_PER_SAMPLE / 1e9, 1),
+                             "ms_per_step_by_kernel": per_kernel}
         if f32_ref is not None:
             res["f32_mfma_path"] = f32_ref
         if world == 1 and not args.no_cpu_baseline:
@@ -414,13 +451,15 @@ def run_train(args, world, rank, dev):
     for _ in range(args.warmup):
         TR.train_one_iter(model, opt, batch, conf, sync)
     barrier()
-    eng.profile = {}             # HIP-event brackets per launch family inside the timed region
+    eng.profile = {} if args.full else None     # HIP-event brackets per launch family inside the timed region
     t0 = time.perf_counter()
     for _ in range(args.steps):
         ld = TR.train_one_iter(model, opt, batch, conf, sync)
     barrier()
     dt = time.perf_counter() - t0
     prof, eng.profile = eng.profile, None
+    if args.dump_outputs and rank == 0:          # the loss terms, and the parameters / BN buffers the step updated
+        dump_outputs(args.dump_outputs, {**ld, **{"state." + k: v for k, v in model.state_dict().items()}})
     losses_all = [float(ld["total_loss"].detach())]
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -432,28 +471,8 @@ def run_train(args, world, rank, dev):
     if rank == 0:
         value = B * world * args.steps / dt
         impl = eng.impl
-        nprod, peak = {"bf16x6": (6, PEAK_BF16_MFMA), "fp16x3": (3, PEAK_BF16_MFMA),
-                       "bf16": (1, PEAK_BF16_MFMA), "bf16op": (1, PEAK_BF16_MFMA)}.get(impl, (1, PEAK_F32_MFMA))
         # fwd + dgrad + wgrad, minus the dgrad of the T+1 stem convs (3->64, 3x3) whose input needs no gradient
         train_flop = 3 * fwd_flop - (model.seqsCnt + 1) * 2 * side * side * 27 * 64
-        # dominant kernel of the step: the 5x5 128->128 weight-gradient launches (6 per step)
-        wg = prof.get(("wgrad", 5, 128, 128), [])
-        wg_ms = sum(a.elapsed_time(b) for a, b in wg) / max(1, len(wg))
-        wg_flop = B * 2 * side * side * 128 * 128 * 25
-        wg_alg = wg_flop / (wg_ms * 1e-3) if wg else None
-        fam = {}
-        for k, v in prof.items():
-            fam.setdefault(k[0], 0.0)
-            fam[k[0]] += sum(a.elapsed_time(b) for a, b in v) / args.steps
-        # the 5x5 128->128 convolution launches of the step (forward + dgrad: the same kernel, 12 launches)
-        cv = prof.get(("fwd", 5, 128, 128), []) + prof.get(("dgrad", 5, 128, 128), [])
-        cv_ms = sum(a.elapsed_time(b) for a, b in cv) / max(1, len(cv))
-        cv_alg = wg_flop / (cv_ms * 1e-3) if cv else None
-        wname = ("wgrad_mfma_f32_kernel<5" if impl == "f32" else
-                 "wgrad_k32_kernel<5, 1, 128, 128" if impl == "fp16x3" else
-                 "wgrad_b16k_kernel<5, 1, 128, 128" if impl == "bf16" else     # (bf16 tensors: csrc/wgrad_b16k.hip)
-                 "wgrad_tr16_kernel<5, 1, 128, 128")
-        traffic, traffic_src = pmc_traffic(wname, "trainbf16" if impl == "bf16" else "train") if B == 2048 and not args.seqs else (None, None)
         res = {
             "metric": "SR train samples/sec (4x4->%dx%d)" % (side, side), "value": round(value, 2), "unit": "samples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -475,28 +494,51 @@ def run_train(args, world, rank, dev):
                        "dist_world_size": dist.get_world_size() if world > 1 else 1,
                        "dist_backend": ("rccl(nccl)" if dist.get_backend() == "nccl" else dist.get_backend()) if world > 1 else None,
                        "conv_impl": impl, "train_GFLOP_per_sample": round(train_flop / 1e9, 3)},
-            "roofline": {"bound": "mfma", "kernel": wname + ",...> (weight gradient of the 5x5 128->128 convs, 6 launches/step)",
-                         "achieved": round(wg_alg / 1e12, 2) if wg_alg else None, "peak": peak / 1e12, "unit": "TFLOP/s",
-                         "frac": round(wg_alg / peak, 4) if wg_alg else None,
-                         "algorithmic_flop_per_launch": wg_flop, "mfma_products_per_mac": nprod,
-                         "mfma_pipe_util": round(wg_alg * nprod / peak, 4) if wg_alg else None,
-                         "avg_launch_ms": round(wg_ms, 3), "launches_timed": len(wg),
-                         "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": B * (2 * 128 * side * side * (2 if impl == "bf16" else 4)) + 128 * 128 * 25 * 4},
-            "roofline_conv": {"bound": "mfma", "kernel": "5x5 128->128 convolution launches of the step (forward + dgrad, 12 per step)",
-                              "achieved": round(cv_alg / 1e12, 2) if cv_alg else None, "peak": peak / 1e12, "unit": "TFLOP/s",
-                              "frac": round(cv_alg / peak, 4) if cv_alg else None, "avg_launch_ms": round(cv_ms, 3),
-                              "launches_timed": len(cv), "mfma_products_per_mac": nprod},
-            "whole_step": {"algorithmic_tflops": round(value / world * train_flop / 1e12, 2),
-                           "frac_of_peak": round(value / world * train_flop / peak, 4),
-                           "mfma_pipe_util": round(value / world * train_flop * nprod / peak, 4),
-                           "algorithmic_vs_f32_mfma_peak": round(value / world * train_flop / PEAK_F32_MFMA, 4),
-                           "ms_per_step_by_family": {k: round(v, 2) for k, v in sorted(fam.items())},
-                           "ms_per_launch": {"%s_k%d_co%d_ci%d" % k: round(sum(a.elapsed_time(b) for a, b in v) / max(1, len(v)), 3)
-                                             for k, v in sorted(prof.items())}},
             "loss": float(ld["total_loss"].detach()),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            nprod, peak = {"bf16x6": (6, PEAK_BF16_MFMA), "fp16x3": (3, PEAK_BF16_MFMA),
+                           "bf16": (1, PEAK_BF16_MFMA), "bf16op": (1, PEAK_BF16_MFMA)}.get(impl, (1, PEAK_F32_MFMA))
+            # dominant kernel of the step: the 5x5 128->128 weight-gradient launches (6 per step)
+            wg = prof.get(("wgrad", 5, 128, 128), [])
+            wg_ms = sum(a.elapsed_time(b) for a, b in wg) / max(1, len(wg))
+            wg_flop = B * 2 * side * side * 128 * 128 * 25
+            wg_alg = wg_flop / (wg_ms * 1e-3) if wg else None
+            fam = {}
+            for k, v in prof.items():
+                fam.setdefault(k[0], 0.0)
+                fam[k[0]] += sum(a.elapsed_time(b) for a, b in v) / args.steps
+            # the 5x5 128->128 convolution launches of the step (forward + dgrad: the same kernel, 12 launches)
+            cv = prof.get(("fwd", 5, 128, 128), []) + prof.get(("dgrad", 5, 128, 128), [])
+            cv_ms = sum(a.elapsed_time(b) for a, b in cv) / max(1, len(cv))
+            cv_alg = wg_flop / (cv_ms * 1e-3) if cv else None
+            wname = ("wgrad_mfma_f32_kernel<5" if impl == "f32" else
+                     "wgrad_k32_kernel<5, 1, 128, 128" if impl == "fp16x3" else
+                     "wgrad_b16k_kernel<5, 1, 128, 128" if impl == "bf16" else     # (bf16 tensors: csrc/wgrad_b16k.hip)
+                     "wgrad_tr16_kernel<5, 1, 128, 128")
+            traffic, traffic_src = pmc_traffic(wname, "trainbf16" if impl == "bf16" else "train") if B == 2048 and not args.seqs else (None, None)
+            res["roofline"] = {"bound": "mfma",
+                               "kernel": wname + ",...> (weight gradient of the 5x5 128->128 convs, 6 launches/step)",
+                               "achieved": round(wg_alg / 1e12, 2) if wg_alg else None, "peak": peak / 1e12, "unit": "TFLOP/s",
+                               "frac": round(wg_alg / peak, 4) if wg_alg else None,
+                               "algorithmic_flop_per_launch": wg_flop, "mfma_products_per_mac": nprod,
+                               "mfma_pipe_util": round(wg_alg * nprod / peak, 4) if wg_alg else None,
+                               "avg_launch_ms": round(wg_ms, 3), "launches_timed": len(wg),
+                               "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": B * (2 * 128 * side * side * (2 if impl == "bf16" else 4)) + 128 * 128 * 25 * 4}
+            res["roofline_conv"] = {"bound": "mfma",
+                                    "kernel": "5x5 128->128 convolution launches of the step (forward + dgrad, 12 per step)",
+                                    "achieved": round(cv_alg / 1e12, 2) if cv_alg else None, "peak": peak / 1e12, "unit": "TFLOP/s",
+                                    "frac": round(cv_alg / peak, 4) if cv_alg else None, "avg_launch_ms": round(cv_ms, 3),
+                                    "launches_timed": len(cv), "mfma_products_per_mac": nprod}
+            res["whole_step"] = {"algorithmic_tflops": round(value / world * train_flop / 1e12, 2),
+                                 "frac_of_peak": round(value / world * train_flop / peak, 4),
+                                 "mfma_pipe_util": round(value / world * train_flop * nprod / peak, 4),
+                                 "algorithmic_vs_f32_mfma_peak": round(value / world * train_flop / PEAK_F32_MFMA, 4),
+                                 "ms_per_step_by_family": {k: round(v, 2) for k, v in sorted(fam.items())},
+                                 "ms_per_launch": {"%s_k%d_co%d_ci%d" % k: round(sum(a.elapsed_time(b) for a, b in v) / max(1, len(v)), 3)
+                                                   for k, v in sorted(prof.items())}}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_seqs_baseline(model, train=True)["cpu_baseline"] if args.seqs else cpu_train_baseline()
         if sync is not None:
             # where in backward each gradient bucket left and how long the step then waited for the wire: the exposed
@@ -583,42 +625,50 @@ def run_tpsf(args, world, rank, dev):
 
     for _ in range(args.warmup):
         step()
-        fwd()
+        if args.full:
+            fwd()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
     barrier()
     dt = time.perf_counter() - t0
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        fwd()
-    barrier()
-    dtf = time.perf_counter() - t1
+    if args.dump_outputs and rank == 0:          # the loss, and the parameters the step updated
+        dump_outputs(args.dump_outputs, {"loss": loss, **{"state." + k: v for k, v in net.state_dict().items()}})
+    dtf = 0.0
+    if args.full:                                # secondary measurement: the forward-only rate, same inputs
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            fwd()
+        barrier()
+        dtf = time.perf_counter() - t1
     if world > 1:
         t = torch.tensor([dt, dtf], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, dtf = float(t[0]), float(t[1])
     if rank == 0:
         value = B * world * args.steps / dt
-        vf = B * world * args.steps / dtf
-        fwd_bytes = 4 * (10000 + 10000 + 9801 + 16 + 48 + 3)      # depth in; HR, psf, LR_degrade out
-        return {
+        res = {
             "metric": "tPSFNet train samples/sec (depth 100x100 -> HR 100x100 + 4x4 taxels)", "value": round(value, 1),
             "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "tPSFNet train step (MLP + separable PSF conv fwd, analytic bwd, Adam), batch/GPU=%d "
                                    "(BASELINE configs[2] shape)" % B, "batch_per_gpu": B, "parallelism": f"replicas x{world}"},
-            "forward_only": {"samples_per_s": round(vf, 1), "ms_per_batch": round(dtf / args.steps * 1e3, 3)},
-            "roofline": {"bound": "hbm", "achieved": round(vf / world * fwd_bytes / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
-                         "frac": round(vf / world * fwd_bytes / 8e12, 4), "traffic": tpsf_traffic(B),
-                         "traffic_unit": "bytes/launch (PMC, profiles/rNN_tpsf_pmc_summary.json; null when the kernel sources changed since)",
-                         "algorithmic_bytes_per_launch": B * fwd_bytes,
-                         "kernel": "tpsf_fwd_mfma_kernel (+ the MLP launches: forward-only rate x %d algorithmic bytes/sample)" % fwd_bytes},
-            "loss": float(loss.detach()),
-            **({"cpu_baseline": cpu_tpsf_baseline()} if world == 1 and not args.no_cpu_baseline else {}),
         }
+        if args.full:
+            vf = B * world * args.steps / dtf
+            fwd_bytes = 4 * (10000 + 10000 + 9801 + 16 + 48 + 3)      # depth in; HR, psf, LR_degrade out
+            res["forward_only"] = {"samples_per_s": round(vf, 1), "ms_per_batch": round(dtf / args.steps * 1e3, 3)}
+            res["roofline"] = {"bound": "hbm", "achieved": round(vf / world * fwd_bytes / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
+                               "frac": round(vf / world * fwd_bytes / 8e12, 4), "traffic": tpsf_traffic(B),
+                               "traffic_unit": "bytes/launch (PMC, profiles/rNN_tpsf_pmc_summary.json; null when the kernel sources changed since)",
+                               "algorithmic_bytes_per_launch": B * fwd_bytes,
+                               "kernel": "tpsf_fwd_mfma_kernel (+ the MLP launches: forward-only rate x %d algorithmic bytes/sample)" % fwd_bytes}
+        res["loss"] = float(loss.detach())
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            res["cpu_baseline"] = cpu_tpsf_baseline()
+        return res
     return None
 
 

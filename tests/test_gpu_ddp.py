@@ -159,7 +159,7 @@ def test_bench_infer_two_ranks_fresh_subprocess_gloo():
     """The DEFAULT bench mode (eval forward: the line the driver's N = 1, 2, 4, 8 scaling run reads) with two ranks, started
     as a fresh process like the train test above: replicas sharded by sample, no data-path collective -- only the
     barrier and the MAX-over-ranks of the timed region.  Checks n_gpus == 2, weak scaling, a positive whole-job rate,
-    a per-GPU step time, the roofline block, and that no CPU baseline / legs ran at N > 1."""
+    a per-GPU step time, the roofline block (`--full`), and that no CPU baseline / legs ran at N > 1."""
     import json
     import os
     import subprocess
@@ -169,7 +169,7 @@ def test_bench_infer_two_ranks_fresh_subprocess_gloo():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--batch", "64", "--steps", "3",
-                        "--warmup", "1"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

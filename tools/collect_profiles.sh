@@ -19,11 +19,11 @@ run() {  # name, rocprof args..., -- bench args
   rm -rf $OUT/$name
   rocprofv3 "$@" > $OUT/$name.log 2>&1
 }
-EVAL="python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-legs"
-TRAIN="python3 bench.py --mode train --steps 3 --warmup 1 --no-cpu-baseline"
-BF16="python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-legs --impl bf16"
-TRAINBF16="python3 bench.py --mode train --impl bf16 --steps 3 --warmup 1 --no-cpu-baseline"
-TPSF="python3 bench.py --mode tpsf --steps 5 --warmup 1 --no-cpu-baseline"
+EVAL="python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-legs"
+TRAIN="python3 bench.py --full --mode train --steps 3 --warmup 1 --no-cpu-baseline"
+BF16="python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-legs --impl bf16"
+TRAINBF16="python3 bench.py --full --mode train --impl bf16 --steps 3 --warmup 1 --no-cpu-baseline"
+TPSF="python3 bench.py --full --mode tpsf --steps 5 --warmup 1 --no-cpu-baseline"
 run eval_stats   --kernel-trace --stats --output-format csv -d $OUT/eval_stats  -- $EVAL
 run eval_fetch   --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/eval_fetch -- $EVAL
 run eval_write   --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/eval_write -- $EVAL

@@ -6,7 +6,7 @@ NAME=$1; shift
 OUT=gpurun_out/prof/$NAME
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --no-cpu-baseline --no-legs "$@" > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --full --no-cpu-baseline --no-legs "$@" > $OUT/run.log 2>&1
 f=$(find $OUT -name '*_kernel_trace.csv' | head -1)
 python3 - "$f" > gpurun_out/prof/${NAME}_last_step.txt <<'PY'
 import csv, sys
