@@ -357,6 +357,15 @@ typedef struct tsr_adam_chunk {
 } tsr_adam_chunk;
 int tsr_adam_l2_multi(const tsr_adam_chunk* chunks, int n_chunks, float lr, double beta1, double beta2, float eps,
                       float weight_decay, int step, void* stream);
+/* The per-step scalars of tsr_adam_l2_multi, {lr, bc1, bc2_sqrt} = {lr, 1 - beta1^step, sqrt(1 - beta2^step)} formed in
+ * double and rounded to float (cpu/trainer.py:361: optimizer.step()'s bias corrections), written to the HOST array out3:
+ * the values the plain launch passes for the same arguments, bit for bit.  Host-only; step is 1-based. */
+int tsr_adam_hyper(float lr, double beta1, double beta2, int step, float* out3);
+/* tsr_adam_l2_multi with its per-step scalars read from the DEVICE array hyper = {lr, bc1, bc2_sqrt} (filled through
+ * tsr_adam_hyper) instead of kernel arguments, so a captured graph replays the step of cpu/trainer.py:361 with the lr
+ * and bias corrections of each replay.  Same kernel body, same arithmetic. */
+int tsr_adam_l2_multi_dev(const tsr_adam_chunk* chunks, int n_chunks, const float* hyper, double beta1, double beta2,
+                          float eps, float weight_decay, void* stream);
 
 /* Per-sample PSNR / SSIM of eval_func (train/tactileSR_train.py:87-94, utility/tools.py:49-81) for B samples
  * of n elements: PSNR = 10log10(max^2/(sum(a-b)^2/psnr_div)) with psnr_div = shape[0]*shape[1] of what the

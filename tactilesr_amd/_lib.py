@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSR_LIB_OVERRIDE") or os.path.join(_HERE, "lib", "libtactilesr_hip.so")   # override: kernel A/B experiments
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _P, _I, _F, _L = c_void_p, c_int, c_float, c_longlong
 
@@ -80,6 +80,8 @@ SIGNATURES = {
     "tsr_mse_fwd_bwd": [_P, _P, _P, _P, _L, _F, _P, _P],
     "tsr_adam_l2_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P],
     "tsr_adam_l2_multi": [_P, _I, _F, c_double, c_double, _F, _F, _I, _P],
+    "tsr_adam_hyper": [_F, c_double, c_double, _I, _P],
+    "tsr_adam_l2_multi_dev": [_P, _I, _P, c_double, c_double, _F, _F, _P],
     "tsr_psnr_ssim": [_P, _P, _I, _I, c_double, c_double, c_double, c_double, _P, _P, _P],
     "tpsf_forward": [_P, _P, _P, _P, _P, _I, _P],
     "tpsf_backward": [_P, _P, _P, _P, _P, _P, _I, _P],

@@ -649,9 +649,11 @@ extern "C" int tsr_adam_l2_step(float* param, const float* grad, float* exp_avg,
 
 // One launch for all parameter tensors: block b owns chunk record b (<= 4096 contiguous elements of one tensor).
 // 16-B accesses when the four pointers are 16-B aligned (torch allocations and the gradient arena are).
-__global__ __launch_bounds__(256) void adam_l2_multi_kernel(const tsr_adam_chunk* __restrict__ chunks, float lr,
-                                                            float b1, float b2, float omb1, float omb2, float eps,
-                                                            float wd, float bc1, float bc2_sqrt) {
+// The body is shared by the two launch forms below: per-step scalars as kernel arguments (tsr_adam_l2_multi) or read
+// from device memory (tsr_adam_l2_multi_dev, the graph-captured step).
+__device__ __forceinline__ void adam_l2_multi_body(const tsr_adam_chunk* __restrict__ chunks, float lr, float b1,
+                                                   float b2, float omb1, float omb2, float eps, float wd, float bc1,
+                                                   float bc2_sqrt) {
   const tsr_adam_chunk c = chunks[blockIdx.x];
   const float step_size = lr / bc1;
   auto upd = [&](float w, float g, float& m, float& v) {
@@ -684,16 +686,51 @@ __global__ __launch_bounds__(256) void adam_l2_multi_kernel(const tsr_adam_chunk
   }
 }
 
+__global__ __launch_bounds__(256) void adam_l2_multi_kernel(const tsr_adam_chunk* __restrict__ chunks, float lr,
+                                                            float b1, float b2, float omb1, float omb2, float eps,
+                                                            float wd, float bc1, float bc2_sqrt) {
+  adam_l2_multi_body(chunks, lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2_sqrt);
+}
+
+// hyper = {lr, bc1, bc2_sqrt} in device memory: a captured graph replays this launch with the values written before
+// each replay instead of the ones of the capture.
+__global__ __launch_bounds__(256) void adam_l2_multi_dev_kernel(const tsr_adam_chunk* __restrict__ chunks,
+                                                                const float* __restrict__ hyper, float b1, float b2,
+                                                                float omb1, float omb2, float eps, float wd) {
+  adam_l2_multi_body(chunks, hyper[0], b1, b2, omb1, omb2, eps, wd, hyper[1], hyper[2]);
+}
+
+// The per-step scalars of both launch forms, formed on the host exactly one way.  betas arrive as doubles and every
+// derived constant is formed in double like torch does on the host: (1.f - 0.999f) is 1.3e-5 off 0.001
+static void adam_hyper(float lr, double beta1, double beta2, int step, float* out3) {
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  out3[0] = lr;
+  out3[1] = (float)bc1;
+  out3[2] = (float)sqrt(bc2);
+}
+
+extern "C" int tsr_adam_hyper(float lr, double beta1, double beta2, int step, float* out3) {
+  if (!out3 || step <= 0) return TSR_ERR_ARG;
+  adam_hyper(lr, beta1, beta2, step, out3);
+  return TSR_OK;
+}
+
 extern "C" int tsr_adam_l2_multi(const tsr_adam_chunk* chunks, int n_chunks, float lr, double beta1, double beta2,
                                  float eps, float weight_decay, int step, void* stream) {
   if (!chunks || n_chunks <= 0 || step <= 0) return TSR_ERR_ARG;
-  // betas arrive as doubles and every derived constant is formed in double like torch does on the host:
-  // (1.f - 0.999f) is 1.3e-5 off 0.001
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  hipLaunchKernelGGL(adam_l2_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, chunks, lr, (float)beta1,
-                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, (float)bc1,
-                     (float)sqrt(bc2));
+  float h[3];
+  adam_hyper(lr, beta1, beta2, step, h);
+  hipLaunchKernelGGL(adam_l2_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, chunks, h[0], (float)beta1,
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, h[1], h[2]);
+  return tsr_check_launch();
+}
+
+extern "C" int tsr_adam_l2_multi_dev(const tsr_adam_chunk* chunks, int n_chunks, const float* hyper, double beta1,
+                                     double beta2, float eps, float weight_decay, void* stream) {
+  if (!chunks || n_chunks <= 0 || !hyper) return TSR_ERR_ARG;
+  hipLaunchKernelGGL(adam_l2_multi_dev_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, chunks, hyper,
+                     (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay);
   return tsr_check_launch();
 }
 

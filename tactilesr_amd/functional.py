@@ -22,15 +22,22 @@ def prepare_target(HR_raw: torch.Tensor, HR_scale_num: float = 10.0, scale_facto
     return out
 
 
+def mse_fwd_bwd(y: torch.Tensor, target: torch.Tensor):
+    """``nn.MSELoss()(y, target)`` and its gradient w.r.t. ``y`` from one pass, outside autograd:
+    (loss as a 1-element tensor, dy)."""
+    y = y.contiguous()
+    t = target.detach().float().contiguous()
+    dy = torch.empty_like(y)
+    loss = torch.empty(1, dtype=torch.float32, device=y.device)
+    work = torch.empty(256, dtype=torch.float64, device=y.device)
+    call("tsr_mse_fwd_bwd", ptr(y), ptr(t), ptr(dy), ptr(loss), _L(y.numel()), _F(1.0), ptr(work), stream())
+    return loss, dy
+
+
 class _MSE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, target):
-        y = y.contiguous()
-        t = target.detach().float().contiguous()
-        dy = torch.empty_like(y)
-        loss = torch.empty(1, dtype=torch.float32, device=y.device)
-        work = torch.empty(256, dtype=torch.float64, device=y.device)
-        call("tsr_mse_fwd_bwd", ptr(y), ptr(t), ptr(dy), ptr(loss), _L(y.numel()), _F(1.0), ptr(work), stream())
+        loss, dy = mse_fwd_bwd(y, target)
         ctx.save_for_backward(dy)
         return loss[0]
 

@@ -10,6 +10,10 @@ Per step the host builds nothing: a device table of (param, grad, exp_avg, exp_a
 elements, is cached per set of live (param, grad) addresses -- with the engine's gradient arena those are the same
 every step -- and the kernel walks it.  Parameters without a gradient are skipped exactly like torch does (the
 Seqs transplant leaves an optimizer holding discarded modules, train/tactileSRSeqs_train.py:74-77).
+
+A captured step (``tactilesr_amd.train.graph.GraphedTrainStep``) goes through ``_captured_step`` /
+``_replay_rows``: the same kernel body launched through ``tsr_adam_l2_multi_dev``, which reads lr and the bias
+corrections from a device buffer that is rewritten on the host before every replay.
 """
 from __future__ import annotations
 
@@ -37,12 +41,16 @@ class Adam(torch.optim.Optimizer):
         self.launches = 0           # kernel launches issued so far (tests: one per step)
         self.table_builds = 0       # device tables built so far (steady state with the gradient arena: exactly one)
 
-    def _table(self, items):
+    def _table(self, items, build=True):
         key = tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel())
                     for p, g, st in items)
         hit = self._tables.get(key)
         if hit is not None:
             return hit
+        if not build:
+            raise TactileSRHipError("tactilesr_amd.optim.Adam: no chunk table for these (param, grad, state) addresses; "
+                                    "building one during a graph capture would be a host-to-device copy -- run an eager "
+                                    "step with the same gradients first")
         recs = []
         for p, g, st in items:
             n = p.numel()
@@ -63,14 +71,11 @@ class Adam(torch.optim.Optimizer):
         self.table_builds += 1
         return self._tables[key]
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _launch_sets(self, advance):
+        """Yields (group, step, [(p, grad, state)]) in launch order: per group, the parameters with a gradient, split by
+        their (1-based) step number.  ``advance`` increments ``state["step"]`` (the eager step, group by group as it
+        launches); without it the step number is the one the next step will use and nothing is created or changed."""
         for group in self.param_groups:
-            b1, b2 = group["betas"]
             by_step = {}
             for p in group["params"]:
                 if p.grad is None:
@@ -80,21 +85,75 @@ class Adam(torch.optim.Optimizer):
                 if not p.is_contiguous():
                     raise TactileSRHipError("tactilesr_amd.optim.Adam needs contiguous parameters")
                 g = p.grad
-                if not g.is_contiguous():
-                    g = p.grad = g.contiguous()
                 st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = torch.tensor(0.0)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["step"] += 1
-                by_step.setdefault(int(st["step"].item()), []).append((p, g, st))     # CPU scalar: no device sync
+                if advance:
+                    if not g.is_contiguous():
+                        g = p.grad = g.contiguous()
+                    if len(st) == 0:
+                        st["step"] = torch.tensor(0.0)
+                        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st["step"] += 1
+                    step = int(st["step"].item())      # CPU scalar: no device sync
+                else:
+                    if len(st) == 0 or not g.is_contiguous():
+                        raise TactileSRHipError("tactilesr_amd.optim.Adam: a captured step needs the optimizer state "
+                                                "and contiguous gradients of an eager step first")
+                    step = int(st["step"].item()) + 1
+                by_step.setdefault(step, []).append((p, g, st))
             for step, items in by_step.items():
-                dev, n_chunks = self._table(items)
-                call("tsr_adam_l2_multi", ptr(dev), _I(n_chunks), _F(group["lr"]), ctypes.c_double(b1), ctypes.c_double(b2),
-                     _F(group["eps"]),
-                     _F(group["weight_decay"]), _I(step), stream())
-                self.launches += 1
+                yield group, step, items
+
+    @torch.no_grad()
+    def _captured_step(self, hyper):
+        """Issue the step into a graph being captured: one ``tsr_adam_l2_multi_dev`` launch per (group, step) set, set
+        ``i`` reading row ``i`` of ``hyper`` (a device float32 tensor of shape (>= sets, 3)).  Chunk tables must exist
+        from an eager step (raises otherwise: building one is a host-to-device copy).  Changes no host state; returns
+        the launch list for ``_replay_rows`` -- it holds the device tables, which the caller keeps alive as long as
+        the graph."""
+        sets = list(self._launch_sets(advance=False))
+        if len(sets) > hyper.shape[0]:
+            raise TactileSRHipError(f"captured Adam step: {len(sets)} launches, hyper buffer has {hyper.shape[0]} rows")
+        launches = []
+        for i, (group, _, items) in enumerate(sets):
+            b1, b2 = group["betas"]
+            dev, n_chunks = self._table(items, build=False)
+            call("tsr_adam_l2_multi_dev", ptr(dev), _I(n_chunks), ctypes.c_void_p(hyper.data_ptr() + 12 * i),
+                 ctypes.c_double(b1), ctypes.c_double(b2), _F(group["eps"]), _F(group["weight_decay"]), stream())
+            launches.append((group, [st for _, _, st in items], dev))
+        return launches
+
+    def _replay_rows(self, launches):
+        """Host side of one replay of a captured step: advance ``state["step"]`` of every parameter the graph updates
+        and return a fresh pinned (len(launches), 3) float32 tensor of {lr, bc1, bc2_sqrt} rows, formed by
+        ``tsr_adam_hyper`` from each group's CURRENT lr -- the floats the eager launch would pass."""
+        rows = torch.empty(len(launches), 3, dtype=torch.float32, pin_memory=True)
+        base = rows.data_ptr()
+        lib = _lib.load()
+        for i, (group, states, _) in enumerate(launches):
+            for st in states:
+                st["step"] += 1
+            b1, b2 = group["betas"]
+            rc = lib.tsr_adam_hyper(_F(group["lr"]), ctypes.c_double(b1), ctypes.c_double(b2),
+                                    _I(int(states[0]["step"].item())), ctypes.c_void_p(base + 12 * i))
+            if rc != 0:
+                raise TactileSRHipError(f"tsr_adam_hyper failed: status {rc}")
+        self.launches += len(launches)
+        return rows
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group, step, items in self._launch_sets(advance=True):
+            b1, b2 = group["betas"]
+            dev, n_chunks = self._table(items)
+            call("tsr_adam_l2_multi", ptr(dev), _I(n_chunks), _F(group["lr"]), ctypes.c_double(b1), ctypes.c_double(b2),
+                 _F(group["eps"]),
+                 _F(group["weight_decay"]), _I(step), stream())
+            self.launches += 1
         # the kernel wrote the parameters behind autograd's back: invalidate cached weight packs (TactileSR._plan)
         _lib.bump_param_epoch()
         return loss

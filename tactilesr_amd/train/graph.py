@@ -1,0 +1,157 @@
+"""HIP-graph replay of the training step for small batches.
+
+At the reference's train batch (``train_batch_size = 32``, config/default.py:46) the HIP train step is ~490 launches
+of a few microseconds each: the HOST's launch path, not the GPU, sets its time.  ``GraphedTrainStep`` captures one
+whole step -- ``train_one_iter``'s zero_grad, ``train_cal_loss``, backward and Adam (train/tactileSR_train.py:41-51,
+cpu/trainer.py:346-362) -- into one HIP graph (``torch.cuda.CUDAGraph``, one stream) and replays it with one host call.
+Opt-in; the plain ``train_one_iter`` path is untouched.
+
+    gstep = GraphedTrainStep(model, optimizer, config, warmup=1)    # model.train() on the ROCm device, optim.Adam
+    loss_dict = gstep((LR, HR_raw))                                 # every call is ONE training step
+
+* The first ``warmup`` calls run ``train_one_iter`` eagerly (real steps): the first backward lays out the gradient
+  arena (tactilesr_amd.ddp), the first Adam step builds its chunk table and the state, one-time kernel attributes are
+  set.  The next call captures a step and replays it once; later calls copy the batch into the static inputs and
+  replay.
+* lr and Adam's bias corrections are NOT frozen by the capture: the graph's Adam launch (``tsr_adam_l2_multi_dev``)
+  reads them from a device buffer that is rewritten before every replay from the optimizer's CURRENT ``group["lr"]``
+  (an lr scheduler works unchanged) and the advanced ``state["step"]``.  The step then has the eager step's results
+  bit for bit, checkpoints included.
+* Recapture: when ``train_impl``, the parameter / buffer / optimizer-state / gradient-arena addresses, the loss
+  config, or the optimizer's baked constants (``betas``, ``eps``, ``weight_decay``) change, the graph is dropped and the
+  next ``warmup`` calls run eagerly again before a new capture.  ``captures`` counts the captures.
+* The returned ``total_loss`` is the graph's static OUTPUT BUFFER (like ``GraphedForward``): the next call overwrites
+  it, so clone it to keep it.  It carries no autograd graph.
+* The captured step is one stream of launches: the train engine's forward and backward and the loss are driven
+  directly, not through the autograd engine (whose per-node streams would fork the capture), so autograd hooks on the
+  parameters do not run in it.
+* Memory: the activations of one step live in the graph's private memory pool, ON TOP of what the eager warm-up left
+  in the caching allocator.  Large batches work but are not the target.
+* Refused (``TactileSRHipError``): eval mode, a batch whose shape / dtype differs from the first call's, an attached
+  ``GradSync`` (no collectives inside a graph), ``engine.profile`` / ``engine.debug`` / ``engine.keep_ctx``, an
+  optimizer other than ``tactilesr_amd.optim.Adam``, a model not on a ROCm device.
+"""
+from __future__ import annotations
+
+import torch
+
+from .. import _lib
+from .. import functional as Fh
+from .._lib import TactileSRHipError
+from ..ddp import note_forward
+from .tactileSR_train import _prep, train_one_iter
+
+_CONFIG_KEYS = ("HR_scale_num", "scale_factor", "seqsCnt", "axisCnt")      # what the captured train_cal_loss bakes in
+
+
+class GraphedTrainStep:
+    def __init__(self, model, optimizer, config, warmup: int = 1):
+        from .. import optim
+        p0 = next(model.parameters(), None)
+        if p0 is None or not p0.is_cuda:
+            raise TactileSRHipError("GraphedTrainStep needs the model on a ROCm device (no CPU fallback)")
+        if not hasattr(model, "train_engine"):
+            raise TactileSRHipError(f"GraphedTrainStep trains a tactilesr_amd.TactileSR, got {type(model).__name__}")
+        if not isinstance(optimizer, optim.Adam):
+            raise TactileSRHipError("GraphedTrainStep needs tactilesr_amd.optim.Adam (its step reads lr and the bias "
+                                    f"corrections from device memory on replay), got {type(optimizer).__name__}")
+        if int(warmup) < 1:
+            raise TactileSRHipError("GraphedTrainStep needs warmup >= 1 (the first backward lays out the gradient arena)")
+        self.model, self.optimizer, self.config = model, optimizer, config
+        self.warmup = int(warmup)
+        self.captures = 0
+        self._sig = None             # (shape, dtype) of LR and HR_raw, fixed by the first call
+        self._drop()
+
+    def _drop(self) -> None:
+        self.graph = None
+        self._out = self._launches = self._hyper = self._LR = self._HR = None
+        self._graph_key = None
+        self._eager_left = self.warmup
+
+    def _key(self):
+        """Everything the captured step bakes in (addresses and constants); lr and the step number are not."""
+        m, opt = self.model, self.optimizer
+        arena = m.train_engine().arena
+        groups = tuple((tuple(g["betas"]), g["eps"], g["weight_decay"],
+                        tuple((p.data_ptr(),) + ((opt.state[p]["exp_avg"].data_ptr(), opt.state[p]["exp_avg_sq"].data_ptr())
+                                                 if len(opt.state[p]) else ()) for p in g["params"]))
+                       for g in opt.param_groups)
+        return (m.train_impl, id(arena), arena.flat.data_ptr() if arena is not None else 0,
+                tuple(t.data_ptr() for t in m.parameters()), tuple(b.data_ptr() for b in m.buffers()), groups,
+                tuple(self.config[k] for k in _CONFIG_KEYS))
+
+    def _check(self, LR, HR) -> None:
+        m = self.model
+        if not m.training:
+            raise TactileSRHipError("GraphedTrainStep replays the TRAIN step: the model is in eval mode")
+        sig = (tuple(LR.shape), LR.dtype, tuple(HR.shape), HR.dtype)
+        if self._sig is None:
+            self._sig = sig
+        elif sig != self._sig:
+            raise TactileSRHipError(f"GraphedTrainStep was set up for batch (LR, HR_raw) of shape / dtype {self._sig}, "
+                                    f"got {sig}")
+        eng = m.train_engine()
+        if eng.grad_sync is not None:
+            raise TactileSRHipError("GraphedTrainStep: a GradSync is attached (no collectives inside a graph)")
+        if eng.profile is not None or eng.debug is not None or eng.keep_ctx:
+            raise TactileSRHipError("GraphedTrainStep: engine.profile / engine.debug / engine.keep_ctx is on "
+                                    "(host-side hooks cannot run inside a replayed graph)")
+
+    def _capture(self, LR, HR) -> None:
+        m, opt = self.model, self.optimizer
+        dev = next(m.parameters()).device
+        self._LR = torch.empty(LR.shape, dtype=LR.dtype, device=dev)
+        self._HR = torch.empty(HR.shape, dtype=HR.dtype, device=dev)
+        # one row of {lr, bc1, bc2_sqrt} per Adam launch; at most one launch per parameter
+        self._hyper = torch.zeros(max(1, sum(len(g["params"]) for g in opt.param_groups)), 3, dtype=torch.float32,
+                                  device=dev)
+        eng = m.train_engine()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph), torch.no_grad():
+            # train_one_iter's launches, with the train engine and the loss driven directly instead of through the
+            # autograd engine: autograd would run the parameters' AccumulateGrad nodes on the stream each node was
+            # created on (the default stream for nodes a live eager graph still holds), i.e. fork the capture.  What
+            # autograd adds on top of these launches is dout = dy * 1 (exact) and the .grad assignment done below;
+            # grad mode is off as inside the autograd Function's forward and backward.
+            LR, HR = _prep((self._LR, self._HR), self.config, dev)
+            if LR.shape[1] != m.seqsCnt * m.axisCnt:
+                raise TactileSRHipError("input channel should be same with seqsCnt x axisCnt!")
+            out, ctx = eng.forward(LR.detach().float().contiguous())
+            m._plan = None                       # as TactileSR.forward: running statistics change in place
+            named = [(n, p) for n, p in m.named_parameters() if p.requires_grad]
+            if named:
+                note_forward(eng, ctx)
+            loss, dy = Fh.mse_fwd_bwd(out.float(), HR)
+            opt.zero_grad()
+            grads = eng.backward(ctx, dy)
+            del ctx
+            missing = [n for n, _ in named if n not in grads]
+            if missing:
+                raise TactileSRHipError(f"backward produced no gradient for {missing[:4]}...")
+            for n, p in named:
+                p.grad = grads[n]                # gradient-arena views, as autograd leaves them
+            launches = opt._captured_step(self._hyper)
+        # the launches hold the Adam chunk tables the graph reads: keep them alive with it
+        self.graph, self._out, self._launches = graph, {"total_loss": loss[0]}, launches
+        self._graph_key = self._key()
+        self.captures += 1
+
+    def __call__(self, batch):
+        LR, HR = batch
+        self._check(LR, HR)
+        if self.graph is not None and self._key() != self._graph_key:
+            self._drop()
+        if self.graph is None and self._eager_left > 0:
+            self._eager_left -= 1
+            return train_one_iter(self.model, self.optimizer, batch, self.config)
+        if self.graph is None:
+            self._capture(LR, HR)
+        self._LR.copy_(LR)
+        self._HR.copy_(HR)
+        rows = self.optimizer._replay_rows(self._launches)       # advances state["step"]; a fresh pinned tensor
+        self._hyper[:rows.shape[0]].copy_(rows, non_blocking=True)
+        self.graph.replay()
+        # the graph's Adam wrote the parameters and its forward the running statistics: cached weight packs are stale
+        _lib.bump_param_epoch()
+        return self._out
