@@ -366,6 +366,26 @@ int tsr_adam_hyper(float lr, double beta1, double beta2, int step, float* out3);
  * and bias corrections of each replay.  Same kernel body, same arithmetic. */
 int tsr_adam_l2_multi_dev(const tsr_adam_chunk* chunks, int n_chunks, const float* hyper, double beta1, double beta2,
                           float eps, float weight_decay, void* stream);
+/* Gradient-norm clipping (cpu/trainer.py:354-356: clip_grad_norm_(model.parameters(), max_norm) before the step).
+ * tsr_grad_norm_multi: the global L2 norm of the GRADIENTS the chunk records point at (chunk.grad, chunk.n; the other
+ * fields are not read) and torch's clip coefficient, written to the DEVICE array out2 = {total_norm, clip_coef}.
+ * Two launches, deterministic (no float atomics): a fixed grid of 256 workgroups writes one double partial each into
+ * work (>= 256 doubles), squaring and summing within a chunk in fp32; one workgroup sums the partials in a fixed order
+ * in double; total_norm = (float)sqrt(sum).  clip_coef is torch's fp32 arithmetic bit for bit:
+ * min((total_norm + 1e-6f).reciprocal() * max_norm, 1) with a clamp that keeps a NaN -- a NaN gradient gives a NaN
+ * norm and coefficient, an Inf gradient an Inf norm and a coefficient of 0.  The norm can differ from torch's by a
+ * few ulps (another summation order).  Edge case: because the partials are combined in double, a norm whose per-chunk
+ * sums of squares stay finite in fp32 but whose total overflows fp32 comes out finite here, where torch returns Inf.
+ * tsr_adam_l2_multi_clip / tsr_adam_l2_multi_dev_clip: tsr_adam_l2_multi / tsr_adam_l2_multi_dev on the clipped
+ * gradient g' = g * clip[0] (one fp32 multiply, rounded on its own), clip a DEVICE pointer to the coefficient
+ * (out2 + 1).  They WRITE g' back through chunk.grad (torch leaves p.grad clipped; skipped where clip[0] == 1, which
+ * is exact).  Result: bit for bit "clip the gradient in fp32, then the plain step". */
+int tsr_grad_norm_multi(const tsr_adam_chunk* chunks, int n_chunks, float max_norm, double* work, float* out2,
+                        void* stream);
+int tsr_adam_l2_multi_clip(const tsr_adam_chunk* chunks, int n_chunks, float lr, double beta1, double beta2, float eps,
+                           float weight_decay, int step, const float* clip, void* stream);
+int tsr_adam_l2_multi_dev_clip(const tsr_adam_chunk* chunks, int n_chunks, const float* hyper, double beta1,
+                               double beta2, float eps, float weight_decay, const float* clip, void* stream);
 
 /* Per-sample PSNR / SSIM of eval_func (train/tactileSR_train.py:87-94, utility/tools.py:49-81) for B samples
  * of n elements: PSNR = 10log10(max^2/(sum(a-b)^2/psnr_div)) with psnr_div = shape[0]*shape[1] of what the

@@ -649,11 +649,14 @@ extern "C" int tsr_adam_l2_step(float* param, const float* grad, float* exp_avg,
 
 // One launch for all parameter tensors: block b owns chunk record b (<= 4096 contiguous elements of one tensor).
 // 16-B accesses when the four pointers are 16-B aligned (torch allocations and the gradient arena are).
-// The body is shared by the two launch forms below: per-step scalars as kernel arguments (tsr_adam_l2_multi) or read
-// from device memory (tsr_adam_l2_multi_dev, the graph-captured step).
+// The body is shared by the launch forms below: per-step scalars as kernel arguments (tsr_adam_l2_multi) or read
+// from device memory (tsr_adam_l2_multi_dev, the graph-captured step), each with or without gradient clipping (CLIP:
+// the gradient is first multiplied by the coefficient *clip that tsr_grad_norm_multi wrote, as its own rounded value,
+// and written back -- torch's clip_grad_norm_ leaves p.grad clipped).  The CLIP = false forms are the plain step.
+template <bool CLIP>
 __device__ __forceinline__ void adam_l2_multi_body(const tsr_adam_chunk* __restrict__ chunks, float lr, float b1,
                                                    float b2, float omb1, float omb2, float eps, float wd, float bc1,
-                                                   float bc2_sqrt) {
+                                                   float bc2_sqrt, const float* __restrict__ clip) {
   const tsr_adam_chunk c = chunks[blockIdx.x];
   const float step_size = lr / bc1;
   auto upd = [&](float w, float g, float& m, float& v) {
@@ -662,11 +665,21 @@ __device__ __forceinline__ void adam_l2_multi_body(const tsr_adam_chunk* __restr
     v = b2 * v + omb2 * gg * gg;
     return w - step_size * (m / (sqrtf(v) / bc2_sqrt + eps));
   };
+  float coef = 1.0f;
+  if (CLIP) coef = clip[0];
+  // coef == 1 multiplies exactly: the gradient already holds the clipped value (NaN != 1: a NaN coefficient writes)
+  const bool write_grad = CLIP && !(coef == 1.0f);
+  float* grad_out = const_cast<float*>(c.grad);
   const bool vec = ((((size_t)c.param | (size_t)c.grad | (size_t)c.exp_avg | (size_t)c.exp_avg_sq) & 15) == 0);
   const int n4 = vec ? (c.n >> 2) : 0;
   for (int i = threadIdx.x; i < n4; i += 256) {
     f32x4 w = ((f32x4*)c.param)[i], m = ((f32x4*)c.exp_avg)[i], v = ((f32x4*)c.exp_avg_sq)[i];
-    const f32x4 g = ((const f32x4*)c.grad)[i];
+    f32x4 g = ((const f32x4*)c.grad)[i];
+    if (CLIP) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) g[j] = __fmul_rn(g[j], coef);
+      if (write_grad) ((f32x4*)grad_out)[i] = g;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float mj = m[j], vj = v[j];
@@ -680,7 +693,12 @@ __device__ __forceinline__ void adam_l2_multi_body(const tsr_adam_chunk* __restr
   }
   for (int i = n4 * 4 + threadIdx.x; i < c.n; i += 256) {
     float m = c.exp_avg[i], v = c.exp_avg_sq[i];
-    c.param[i] = upd(c.param[i], c.grad[i], m, v);
+    float g = c.grad[i];
+    if (CLIP) {
+      g = __fmul_rn(g, coef);
+      if (write_grad) grad_out[i] = g;
+    }
+    c.param[i] = upd(c.param[i], g, m, v);
     c.exp_avg[i] = m;
     c.exp_avg_sq[i] = v;
   }
@@ -689,7 +707,7 @@ __device__ __forceinline__ void adam_l2_multi_body(const tsr_adam_chunk* __restr
 __global__ __launch_bounds__(256) void adam_l2_multi_kernel(const tsr_adam_chunk* __restrict__ chunks, float lr,
                                                             float b1, float b2, float omb1, float omb2, float eps,
                                                             float wd, float bc1, float bc2_sqrt) {
-  adam_l2_multi_body(chunks, lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2_sqrt);
+  adam_l2_multi_body<false>(chunks, lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2_sqrt, nullptr);
 }
 
 // hyper = {lr, bc1, bc2_sqrt} in device memory: a captured graph replays this launch with the values written before
@@ -697,7 +715,22 @@ __global__ __launch_bounds__(256) void adam_l2_multi_kernel(const tsr_adam_chunk
 __global__ __launch_bounds__(256) void adam_l2_multi_dev_kernel(const tsr_adam_chunk* __restrict__ chunks,
                                                                 const float* __restrict__ hyper, float b1, float b2,
                                                                 float omb1, float omb2, float eps, float wd) {
-  adam_l2_multi_body(chunks, hyper[0], b1, b2, omb1, omb2, eps, wd, hyper[1], hyper[2]);
+  adam_l2_multi_body<false>(chunks, hyper[0], b1, b2, omb1, omb2, eps, wd, hyper[1], hyper[2], nullptr);
+}
+
+// The clipping forms of the two kernels above: clip[0] is the coefficient tsr_grad_norm_multi wrote.
+__global__ __launch_bounds__(256) void adam_l2_multi_clip_kernel(const tsr_adam_chunk* __restrict__ chunks, float lr,
+                                                                 float b1, float b2, float omb1, float omb2, float eps,
+                                                                 float wd, float bc1, float bc2_sqrt,
+                                                                 const float* __restrict__ clip) {
+  adam_l2_multi_body<true>(chunks, lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2_sqrt, clip);
+}
+
+__global__ __launch_bounds__(256) void adam_l2_multi_dev_clip_kernel(const tsr_adam_chunk* __restrict__ chunks,
+                                                                     const float* __restrict__ hyper, float b1,
+                                                                     float b2, float omb1, float omb2, float eps,
+                                                                     float wd, const float* __restrict__ clip) {
+  adam_l2_multi_body<true>(chunks, hyper[0], b1, b2, omb1, omb2, eps, wd, hyper[1], hyper[2], clip);
 }
 
 // The per-step scalars of both launch forms, formed on the host exactly one way.  betas arrive as doubles and every
@@ -731,6 +764,91 @@ extern "C" int tsr_adam_l2_multi_dev(const tsr_adam_chunk* chunks, int n_chunks,
   if (!chunks || n_chunks <= 0 || !hyper) return TSR_ERR_ARG;
   hipLaunchKernelGGL(adam_l2_multi_dev_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, chunks, hyper,
                      (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay);
+  return tsr_check_launch();
+}
+
+extern "C" int tsr_adam_l2_multi_clip(const tsr_adam_chunk* chunks, int n_chunks, float lr, double beta1,
+                                      double beta2, float eps, float weight_decay, int step, const float* clip,
+                                      void* stream) {
+  if (!chunks || n_chunks <= 0 || step <= 0 || !clip) return TSR_ERR_ARG;
+  float h[3];
+  adam_hyper(lr, beta1, beta2, step, h);
+  hipLaunchKernelGGL(adam_l2_multi_clip_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, chunks, h[0],
+                     (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, h[1],
+                     h[2], clip);
+  return tsr_check_launch();
+}
+
+extern "C" int tsr_adam_l2_multi_dev_clip(const tsr_adam_chunk* chunks, int n_chunks, const float* hyper,
+                                          double beta1, double beta2, float eps, float weight_decay, const float* clip,
+                                          void* stream) {
+  if (!chunks || n_chunks <= 0 || !hyper || !clip) return TSR_ERR_ARG;
+  hipLaunchKernelGGL(adam_l2_multi_dev_clip_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, chunks, hyper,
+                     (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, clip);
+  return tsr_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------
+// Global L2 norm of the gradients a chunk table points at, and torch's clip coefficient (torch.nn.utils.
+// clip_grad_norm_, cpu/trainer.py:356): deterministic, no float atomics.  Workgroup b walks chunks b, b + GN_BLOCKS,
+// ...: each thread squares and sums its (<= 16) elements of a chunk in fp32 with 16-B loads and adds that to a double
+// accumulator; the workgroup combines its threads in a fixed tree into part[b].  One workgroup then sums the partials
+// in a fixed tree and forms {total_norm, clip_coef}.
+// ------------------------------------------------------------------------------------------
+#define GN_BLOCKS 256      // partials of tsr_grad_norm_multi (its work buffer holds GN_BLOCKS doubles)
+
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const tsr_adam_chunk* __restrict__ chunks,
+                                                                int n_chunks, double* __restrict__ part) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (int b = blockIdx.x; b < n_chunks; b += gridDim.x) {
+    const tsr_adam_chunk c = chunks[b];
+    float cs = 0.f;
+    const int n4 = (((size_t)c.grad & 15) == 0) ? (c.n >> 2) : 0;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      const f32x4 g = ((const f32x4*)c.grad)[i];
+      cs = fmaf(g[0], g[0], cs);
+      cs = fmaf(g[1], g[1], cs);
+      cs = fmaf(g[2], g[2], cs);
+      cs = fmaf(g[3], g[3], cs);
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < c.n; i += 256) cs = fmaf(c.grad[i], c.grad[i], cs);
+    s += (double)cs;
+  }
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int k = 128; k > 0; k >>= 1) {
+    if (threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
+}
+
+__global__ __launch_bounds__(GN_BLOCKS) void grad_norm_final_kernel(const double* __restrict__ part, float max_norm,
+                                                                    float* __restrict__ out2) {
+  __shared__ double sh[GN_BLOCKS];
+  sh[threadIdx.x] = part[threadIdx.x];
+  __syncthreads();
+  for (int k = GN_BLOCKS / 2; k > 0; k >>= 1) {
+    if (threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(sh[0]);
+    // torch: clip_coef = max_norm / (total_norm + 1e-6) is Tensor.__rdiv__ = (total_norm + 1e-6).reciprocal() *
+    // max_norm, all fp32; then clamp(max=1.0), which keeps a NaN (fminf would not)
+    const float coef = __fmul_rn(1.0f / __fadd_rn(norm, 1e-6f), max_norm);
+    out2[0] = norm;
+    out2[1] = coef > 1.0f ? 1.0f : coef;
+  }
+}
+
+extern "C" int tsr_grad_norm_multi(const tsr_adam_chunk* chunks, int n_chunks, float max_norm, double* work,
+                                   float* out2, void* stream) {
+  if (!chunks || n_chunks <= 0 || !work || !out2) return TSR_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(GN_BLOCKS), dim3(256), 0, st, chunks, n_chunks, work);
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(GN_BLOCKS), 0, st, work, max_norm, out2);
   return tsr_check_launch();
 }
 

@@ -14,6 +14,12 @@ Seqs transplant leaves an optimizer holding discarded modules, train/tactileSRSe
 A captured step (``tactilesr_amd.train.graph.GraphedTrainStep``) goes through ``_captured_step`` /
 ``_replay_rows``: the same kernel body launched through ``tsr_adam_l2_multi_dev``, which reads lr and the bias
 corrections from a device buffer that is rewritten on the host before every replay.
+
+Gradient-norm clipping (the reference trainer's ``clip_grad_norm``, cpu/trainer.py:354-356): ``step_clipped(max_norm)``
+is ``torch.nn.utils.clip_grad_norm_(<the parameters with a gradient>, max_norm); step()`` without a host sync -- one
+``tsr_grad_norm_multi`` (two kernels) over a chunk table of every group's gradients writes {total_norm, clip_coef} to a
+device array, then every (group, step) set runs ``tsr_adam_l2_multi_clip``, which scales the gradient by that
+coefficient, writes it back (torch leaves ``p.grad`` clipped) and takes the plain step on it.
 """
 from __future__ import annotations
 
@@ -25,6 +31,8 @@ from . import _lib
 from ._lib import call, ptr, stream, c_int as _I, c_float as _F, TactileSRHipError
 
 CHUNK = 4096
+GN_PARTIALS = 256     # tsr_grad_norm_multi: one double partial per workgroup of its first kernel
+GN_LAUNCHES = 2       # kernels one tsr_grad_norm_multi call issues
 
 
 class _Rec(ctypes.Structure):         # mirror of tsr_adam_chunk (include/tactilesr_hip.h)
@@ -104,13 +112,31 @@ class Adam(torch.optim.Optimizer):
             for step, items in by_step.items():
                 yield group, step, items
 
+    def _grad_norm(self, sets, max_norm, out, work, build=True):
+        """Issue ``tsr_grad_norm_multi`` over the gradients of every (param, grad) item of ``sets`` (as
+        ``_launch_sets`` yields them): out = {total_norm, clip_coef} (a device float32 tensor of >= 2 elements), work
+        a device float64 tensor of >= GN_PARTIALS elements.  Returns the chunk table the launch reads."""
+        if out.dtype != torch.float32 or out.numel() < 2 or work.dtype != torch.float64 or work.numel() < GN_PARTIALS:
+            raise TactileSRHipError("gradient norm: out needs 2 float32 elements, work GN_PARTIALS float64 elements")
+        dev, n_chunks = self._table([it for _, _, items in sets for it in items], build=build)
+        call("tsr_grad_norm_multi", ptr(dev), _I(n_chunks), _F(max_norm), ptr(work), ptr(out), stream())
+        return dev
+
     @torch.no_grad()
-    def _captured_step(self, hyper):
+    def _captured_grad_norm(self, max_norm, out, work):
+        """``_grad_norm`` issued into a graph being captured, over the gradients the next step updates.  The chunk
+        table must exist from an eager clipped step (raises otherwise).  Returns the table, which the caller keeps
+        alive as long as the graph; a replay issues GN_LAUNCHES kernels."""
+        return self._grad_norm(list(self._launch_sets(advance=False)), max_norm, out, work, build=False)
+
+    @torch.no_grad()
+    def _captured_step(self, hyper, clip=None):
         """Issue the step into a graph being captured: one ``tsr_adam_l2_multi_dev`` launch per (group, step) set, set
-        ``i`` reading row ``i`` of ``hyper`` (a device float32 tensor of shape (>= sets, 3)).  Chunk tables must exist
-        from an eager step (raises otherwise: building one is a host-to-device copy).  Changes no host state; returns
-        the launch list for ``_replay_rows`` -- it holds the device tables, which the caller keeps alive as long as
-        the graph."""
+        ``i`` reading row ``i`` of ``hyper`` (a device float32 tensor of shape (>= sets, 3)).  With ``clip`` (a device
+        float32 tensor whose first element is the coefficient ``_captured_grad_norm`` writes, i.e. ``out[1:]``) the
+        launches are ``tsr_adam_l2_multi_dev_clip``.  Chunk tables must exist from an eager step (raises otherwise:
+        building one is a host-to-device copy).  Changes no host state; returns the launch list for ``_replay_rows``
+        -- it holds the device tables, which the caller keeps alive as long as the graph."""
         sets = list(self._launch_sets(advance=False))
         if len(sets) > hyper.shape[0]:
             raise TactileSRHipError(f"captured Adam step: {len(sets)} launches, hyper buffer has {hyper.shape[0]} rows")
@@ -118,8 +144,12 @@ class Adam(torch.optim.Optimizer):
         for i, (group, _, items) in enumerate(sets):
             b1, b2 = group["betas"]
             dev, n_chunks = self._table(items, build=False)
-            call("tsr_adam_l2_multi_dev", ptr(dev), _I(n_chunks), ctypes.c_void_p(hyper.data_ptr() + 12 * i),
-                 ctypes.c_double(b1), ctypes.c_double(b2), _F(group["eps"]), _F(group["weight_decay"]), stream())
+            args = (ptr(dev), _I(n_chunks), ctypes.c_void_p(hyper.data_ptr() + 12 * i), ctypes.c_double(b1),
+                    ctypes.c_double(b2), _F(group["eps"]), _F(group["weight_decay"]))
+            if clip is None:
+                call("tsr_adam_l2_multi_dev", *args, stream())
+            else:
+                call("tsr_adam_l2_multi_dev_clip", *args, ptr(clip), stream())
             launches.append((group, [st for _, _, st in items], dev))
         return launches
 
@@ -157,3 +187,29 @@ class Adam(torch.optim.Optimizer):
         # the kernel wrote the parameters behind autograd's back: invalidate cached weight packs (TactileSR._plan)
         _lib.bump_param_epoch()
         return loss
+
+    @torch.no_grad()
+    def step_clipped(self, max_norm: float) -> torch.Tensor:
+        """``torch.nn.utils.clip_grad_norm_(<the parameters of this optimizer with a gradient>, max_norm); step()``
+        (cpu/trainer.py:354-361) in GN_LAUNCHES + one launch per (group, step) set, without a host sync.  Returns the
+        total norm of the gradients before clipping as a 0-dim device tensor (fresh storage every call); the gradients
+        are left clipped, as torch leaves them.  The coefficient is torch's for that norm bit for bit; a NaN gradient
+        makes every gradient NaN, an Inf one makes the finite ones 0 (torch's rules)."""
+        sets = list(self._launch_sets(advance=True))
+        if not sets:                      # nothing to clip or step (torch: a norm of 0)
+            _lib.bump_param_epoch()
+            return torch.tensor(0.0)
+        device = sets[0][2][0][0].device
+        out = torch.empty(2, dtype=torch.float32, device=device)           # {total_norm, clip_coef}
+        work = torch.empty(GN_PARTIALS, dtype=torch.float64, device=device)
+        self._grad_norm(sets, max_norm, out, work)
+        self.launches += GN_LAUNCHES
+        coef = out[1:]
+        for group, step, items in sets:
+            b1, b2 = group["betas"]
+            dev, n_chunks = self._table(items)
+            call("tsr_adam_l2_multi_clip", ptr(dev), _I(n_chunks), _F(group["lr"]), ctypes.c_double(b1),
+                 ctypes.c_double(b2), _F(group["eps"]), _F(group["weight_decay"]), _I(step), ptr(coef), stream())
+            self.launches += 1
+        _lib.bump_param_epoch()
+        return out[0]

@@ -18,8 +18,8 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
   (an lr scheduler works unchanged) and the advanced ``state["step"]``.  The step then has the eager step's results
   bit for bit, checkpoints included.
 * Recapture: when ``train_impl``, the parameter / buffer / optimizer-state / gradient-arena addresses, the loss
-  config, or the optimizer's baked constants (``betas``, ``eps``, ``weight_decay``) change, the graph is dropped and the
-  next ``warmup`` calls run eagerly again before a new capture.  ``captures`` counts the captures.
+  config, the optimizer's baked constants (``betas``, ``eps``, ``weight_decay``) or ``clip_grad_norm`` change, the
+  graph is dropped and the next ``warmup`` calls run eagerly again before a new capture.  ``captures`` counts the captures.
 * The returned ``total_loss`` is the graph's static OUTPUT BUFFER (like ``GraphedForward``): the next call overwrites
   it, so clone it to keep it.  It carries no autograd graph.
 * The captured step is one stream of launches: the train engine's forward and backward and the loss are driven
@@ -27,9 +27,19 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
   parameters do not run in it.
 * Memory: the activations of one step live in the graph's private memory pool, ON TOP of what the eager warm-up left
   in the caching allocator.  Large batches work but are not the target.
+* Gradient-norm clipping: ``GraphedTrainStep(..., clip_grad_norm=c)`` with ``c > 0`` is ``train_one_iter(...,
+  clip_grad_norm=c)`` (the reference ``Trainer(clip_grad_norm=c)``, cpu/trainer.py:354-356).  The eager warm-up calls
+  pass ``c`` on; the capture issues the norm kernels (``tsr_grad_norm_multi``, into a static work buffer and a static
+  {total_norm, clip_coef} array allocated before the capture) and the Adam launches in their clipping form
+  (``tsr_adam_l2_multi_dev_clip``, reading the coefficient from that array), so every replay clips with the norm of
+  its own gradients.  ``c`` is baked into the graph like ``betas`` / ``eps`` / ``weight_decay``: assigning another
+  ``gstep.clip_grad_norm`` drops the graph and recaptures.  Clipping needs the fused path's condition: every trainable
+  model parameter is stepped by the optimizer (refused otherwise, e.g. the Seqs transplant, whose new parameters are
+  not in the optimizer).  ``c <= 0`` (the default) captures the step as before.
 * Refused (``TactileSRHipError``): eval mode, a batch whose shape / dtype differs from the first call's, an attached
   ``GradSync`` (no collectives inside a graph), ``engine.profile`` / ``engine.debug`` / ``engine.keep_ctx``, an
-  optimizer other than ``tactilesr_amd.optim.Adam``, a model not on a ROCm device.
+  optimizer other than ``tactilesr_amd.optim.Adam``, a model not on a ROCm device, clipping where a trainable model
+  parameter is not in the optimizer.
 """
 from __future__ import annotations
 
@@ -37,6 +47,7 @@ import torch
 
 from .. import _lib
 from .. import functional as Fh
+from .. import optim as opt_mod
 from .._lib import TactileSRHipError
 from ..ddp import note_forward
 from .tactileSR_train import _prep, train_one_iter
@@ -45,7 +56,7 @@ _CONFIG_KEYS = ("HR_scale_num", "scale_factor", "seqsCnt", "axisCnt")      # wha
 
 
 class GraphedTrainStep:
-    def __init__(self, model, optimizer, config, warmup: int = 1):
+    def __init__(self, model, optimizer, config, warmup: int = 1, clip_grad_norm: float = 0.0):
         from .. import optim
         p0 = next(model.parameters(), None)
         if p0 is None or not p0.is_cuda:
@@ -59,6 +70,7 @@ class GraphedTrainStep:
             raise TactileSRHipError("GraphedTrainStep needs warmup >= 1 (the first backward lays out the gradient arena)")
         self.model, self.optimizer, self.config = model, optimizer, config
         self.warmup = int(warmup)
+        self.clip_grad_norm = float(clip_grad_norm)
         self.captures = 0
         self._sig = None             # (shape, dtype) of LR and HR_raw, fixed by the first call
         self._drop()
@@ -66,6 +78,7 @@ class GraphedTrainStep:
     def _drop(self) -> None:
         self.graph = None
         self._out = self._launches = self._hyper = self._LR = self._HR = None
+        self._norm = self._norm_work = self._norm_table = None
         self._graph_key = None
         self._eager_left = self.warmup
 
@@ -79,7 +92,7 @@ class GraphedTrainStep:
                        for g in opt.param_groups)
         return (m.train_impl, id(arena), arena.flat.data_ptr() if arena is not None else 0,
                 tuple(t.data_ptr() for t in m.parameters()), tuple(b.data_ptr() for b in m.buffers()), groups,
-                tuple(self.config[k] for k in _CONFIG_KEYS))
+                tuple(self.config[k] for k in _CONFIG_KEYS), self.clip_grad_norm)
 
     def _check(self, LR, HR) -> None:
         m = self.model
@@ -97,6 +110,12 @@ class GraphedTrainStep:
         if eng.profile is not None or eng.debug is not None or eng.keep_ctx:
             raise TactileSRHipError("GraphedTrainStep: engine.profile / engine.debug / engine.keep_ctx is on "
                                     "(host-side hooks cannot run inside a replayed graph)")
+        if self.clip_grad_norm > 0:
+            stepped = {id(p) for g in self.optimizer.param_groups for p in g["params"]}
+            if any(p.requires_grad and id(p) not in stepped for p in m.parameters()):
+                raise TactileSRHipError("GraphedTrainStep: clip_grad_norm needs every trainable model parameter in the "
+                                        "optimizer (the norm is taken over model.parameters(), the fused clip over "
+                                        "the optimizer's)")
 
     def _capture(self, LR, HR) -> None:
         m, opt = self.model, self.optimizer
@@ -106,6 +125,10 @@ class GraphedTrainStep:
         # one row of {lr, bc1, bc2_sqrt} per Adam launch; at most one launch per parameter
         self._hyper = torch.zeros(max(1, sum(len(g["params"]) for g in opt.param_groups)), 3, dtype=torch.float32,
                                   device=dev)
+        clip = self.clip_grad_norm > 0
+        if clip:                                 # {total_norm, clip_coef} and the partials of the norm kernels
+            self._norm = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._norm_work = torch.zeros(opt_mod.GN_PARTIALS, dtype=torch.float64, device=dev)
         eng = m.train_engine()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph), torch.no_grad():
@@ -131,9 +154,12 @@ class GraphedTrainStep:
                 raise TactileSRHipError(f"backward produced no gradient for {missing[:4]}...")
             for n, p in named:
                 p.grad = grads[n]                # gradient-arena views, as autograd leaves them
-            launches = opt._captured_step(self._hyper)
-        # the launches hold the Adam chunk tables the graph reads: keep them alive with it
+            if clip:     # _check holds: zero_grad cleared every other gradient, so fused_clip_applies(m, opt) too
+                norm_table = opt._captured_grad_norm(self.clip_grad_norm, self._norm, self._norm_work)
+            launches = opt._captured_step(self._hyper, clip=self._norm[1:] if clip else None)
+        # the launches (and the norm launch) hold the Adam chunk tables the graph reads: keep them alive with it
         self.graph, self._out, self._launches = graph, {"total_loss": loss[0]}, launches
+        self._norm_table = norm_table if clip else None
         self._graph_key = self._key()
         self.captures += 1
 
@@ -144,12 +170,14 @@ class GraphedTrainStep:
             self._drop()
         if self.graph is None and self._eager_left > 0:
             self._eager_left -= 1
-            return train_one_iter(self.model, self.optimizer, batch, self.config)
+            return train_one_iter(self.model, self.optimizer, batch, self.config, clip_grad_norm=self.clip_grad_norm)
         if self.graph is None:
             self._capture(LR, HR)
         self._LR.copy_(LR)
         self._HR.copy_(HR)
         rows = self.optimizer._replay_rows(self._launches)       # advances state["step"]; a fresh pinned tensor
+        if self._norm_table is not None:
+            self.optimizer.launches += opt_mod.GN_LAUNCHES
         self._hyper[:rows.shape[0]].copy_(rows, non_blocking=True)
         self.graph.replay()
         # the graph's Adam wrote the parameters and its forward the running statistics: cached weight packs are stale

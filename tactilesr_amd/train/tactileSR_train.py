@@ -3,7 +3,8 @@ HIP path.  The reference subclasses its vendored ``cpu.Trainer`` (out of scope h
 path needs from it are the three functions below with the same argument meaning:
 
   * ``train_cal_loss(model, batch, config)``  <->  Trainer_tactileSR.train_cal_loss   (:41-51)
-  * ``train_one_iter(model, optimizer, batch, config)``  <->  Trainer.train_one_iter  (cpu/trainer.py:346-362)
+  * ``train_one_iter(model, optimizer, batch, config)``  <->  Trainer.train_one_iter  (cpu/trainer.py:346-362),
+    its ``clip_grad_norm`` option included
   * ``eval_func(model, test_loader, config)``  <->  eval_func (:66-101), returning the three averages
     the reference only logs.
 """
@@ -36,9 +37,30 @@ def train_cal_loss(model, batch, config):
     return loss, {"total_loss": loss}
 
 
-def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite=False, cur_iter=None):
+def fused_clip_applies(model, optimizer) -> bool:
+    """Whether ``optimizer.step_clipped`` clips exactly what the reference clips: the optimizer is
+    ``tactilesr_amd.optim.Adam`` and the model parameters with a gradient are, by identity, the parameters it steps
+    (those of its groups with a gradient).  Host-only."""
+    from ..optim import Adam
+    if not isinstance(optimizer, Adam):
+        return False
+    have = {id(p) for p in model.parameters() if p.grad is not None}
+    stepped = {id(p) for g in optimizer.param_groups for p in g["params"] if p.grad is not None}
+    return have == stepped
+
+
+def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite=False, cur_iter=None,
+                   clip_grad_norm=0.0):
     """zero_grad -> backward -> step, the order of cpu/trainer.py:352-361.  ``grad_sync`` (optional)
     is called between backward and step (data-parallel gradient averaging: tactilesr_amd.ddp).
+
+    ``clip_grad_norm > 0`` clips the gradients to that global L2 norm before the step, after ``grad_sync`` (the
+    reference ``Trainer(clip_grad_norm=...)``, cpu/trainer.py:354-356: ``clip_grad_norm_(model.parameters(), c)``);
+    ``<= 0``, the default, leaves the step as it is.  With ``tactilesr_amd.optim.Adam`` stepping exactly the model's
+    parameters that have a gradient, the clip is fused into the step (``Adam.step_clipped``: a norm kernel, then the
+    Adam launch scales the gradients); otherwise -- another optimizer, or one that holds only part of them (the Seqs
+    transplant, train/tactileSRSeqs_train.py:74-77) -- the reference's own two calls run:
+    ``torch.nn.utils.clip_grad_norm_(model.parameters(), c)``, then ``optimizer.step()``.
 
     ``check_finite=True`` reproduces the reference trainer's per-iteration failure check
     (``Trainer._log_iter_metrics``, cpu/trainer.py:259,280-284): the loss is read back (a host sync, like the
@@ -51,7 +73,14 @@ def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite
     losses.backward()
     if grad_sync is not None:
         grad_sync()
-    optimizer.step()
+    if clip_grad_norm > 0:
+        if fused_clip_applies(model, optimizer):
+            optimizer.step_clipped(clip_grad_norm)
+        else:
+            torch.nn.utils.clip_grad_norm_(model.parameters(), clip_grad_norm)
+            optimizer.step()
+    else:
+        optimizer.step()
     if check_finite:
         import math
         value = float(losses.detach())
