@@ -310,9 +310,16 @@ int tsr_bn_bwd_apply(float* g, int g_ctot, int g_coff, const float* z, int z_cto
                      const float* c1, const float* c2, const float* c3, int C, int B, int HW,
                      float* out_amax /* optional: max|g| after the update */, void* stream);
 
-/* Backward of tsr_stem_fwd's conv weight: slab[s][64][3][3][3] partials (taxels carry no gradient). */
+/* Backward of tsr_stem_fwd's conv weight: slab[s][64][3][3][3] partials (the taxel gradient is tsr_stem_dgrad). */
 int tsr_stem_wgrad(const float* lr, int lr_ctot, int lr_coff, int hin, int win, int sf,
                    const float* dz, int dz_ctot, int dz_coff, float* slab, int nsplit, int B, void* stream);
+/* Taxel gradient of the stem (reference model/tactileSR_model.py:35-37,60-61: Upsample(bilinear, align_corners=False) +
+ * Conv2d(3 -> 64, 3x3, pad 1, no bias)): dx = up_sf^T(conv3x3^T(dz; w_oihw)) for the 64 CB16 channels
+ * dz_coff .. dz_coff + 63 of dz (pre-BN / pre-ReLU-masked gradient).  dx is NCHW fp32 (B, dx_ctot, hin, win); channels
+ * dx_coff .. dx_coff + 2 are stored (accumulate = 0) or added to (accumulate = 1).  hin, win <= 4; fp32 arithmetic, one
+ * workgroup per image, bit-reproducible. */
+int tsr_stem_dgrad(const float* w_oihw, const float* dz, int dz_ctot, int dz_coff, int hin, int win, int sf,
+                   float* dx, int dx_ctot, int dx_coff, int accumulate, int B, void* stream);
 /* Backward of tsr_head_fwd: dz_h0 = dgrad(dout*[out>0]) * [h0>0] (CB16) and weight partials
  * wslab[s][cin][3][3]. */
 int tsr_head_bwd(const float* dout, const float* out, const float* h0, int h_ctot, int cin,
@@ -326,6 +333,9 @@ int tsr_cb16_stats_b16(const void* z, int z_ctot, int z_coff, int B, int HW, flo
                        void* stream);
 int tsr_bn_bwd_apply_b16(void* g, int g_ctot, int g_coff, const void* z, int z_ctot, int z_coff,
                          const float* c1, const float* c2, const float* c3, int C, int B, int HW, void* stream);
+/* tsr_stem_dgrad on a bf16 CB16 dz (fp32 arithmetic, fp32 dx). */
+int tsr_stem_dgrad_b16(const float* w_oihw, const void* dz, int dz_ctot, int dz_coff, int hin, int win, int sf,
+                       float* dx, int dx_ctot, int dx_coff, int accumulate, int B, void* stream);
 /* out[B][C/16][HW][16] (bf16) = bf16(relu(fp32(z) * scale + shift)) of channels z_coff .. z_coff + C of the stored
  * pre-BatchNorm tensor: the MATERIALISED form of a virtual activation.  tsr_conv2d_wgrad_bf16s (planes = -1) runs the 3x3 /
  * 5x5 launches for which tsr_conv2d_wgrad_b16k(cout, cin, ks) returns 1 on csrc/wgrad_b16k.hip (operands straight from HBM

@@ -68,6 +68,7 @@ SIGNATURES = {
     "tsr_bn_bwd_finalize": [_P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "tsr_bn_bwd_apply": [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
     "tsr_stem_wgrad": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
+    "tsr_stem_dgrad": [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P],
     "tsr_head_bwd": [_P, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P],
     "tsr_cb16_stats_b16": [_P, _I, _I, _I, _I, _P, _P, _P],
     "tsr_bn_bwd_apply_b16": [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P],
@@ -75,6 +76,7 @@ SIGNATURES = {
     "tsr_conv2d_wgrad_b16k": [_I, _I, _I],
     "tsr_conv2d_ex_fwd1x1_b16k": [_I, _I],
     "tsr_stem_wgrad_b16": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
+    "tsr_stem_dgrad_b16": [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P],
     "tsr_head_bwd_b16": [_P, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P],
     "tsr_target_prep": [_P, _P, _F, _I, _I, _I, _I, _I, _P],
     "tsr_mse_fwd_bwd": [_P, _P, _P, _P, _L, _F, _P, _P],

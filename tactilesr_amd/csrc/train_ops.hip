@@ -224,7 +224,7 @@ extern "C" int tsr_bn_bwd_apply_b16(void* g, int g_ctot, int g_coff, const void*
 }
 
 // ------------------------------------------------------------------------------------------
-// stem backward: dW[64][3][3][3] of Upsample+Conv2d(3->64) (no dgrad: taxels carry no grad)
+// stem backward: dW[64][3][3][3] of Upsample+Conv2d(3->64) (the taxel gradient: stem_dgrad_kernel below)
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void bilin_src_t(int dst, float scale, int n_in, int& i0, int& i1, float& lam) {
   float src = scale * ((float)dst + 0.5f) - 0.5f;
@@ -366,6 +366,150 @@ extern "C" int tsr_stem_wgrad_b16(const float* lr, int lr_ctot, int lr_coff, int
                                   const void* dz, int dz_ctot, int dz_coff, float* slab, int nsplit, int B,
                                   void* stream) {
   return stem_wgrad_impl(lr, lr_ctot, lr_coff, hin, win, sf, (const float*)dz, dz_ctot, dz_coff, slab, nsplit, B, stream, true);
+}
+
+// ------------------------------------------------------------------------------------------
+// stem data gradient: dx[3][hin][win] of z = conv3x3(up_sf(x), W) given dz (reference model/tactileSR_model.py:35-37,60-61)
+//   t[c][kh][kw](p) = sum_co W[co][c][kh][kw] dz[co][p]      -- dz pixel p feeds dup at q = p + (kh - 1, kw - 1)
+//   dx[c][i][j]    += A_y[q_y][i] A_x[q_x][j] t[c][kh][kw](p) for q inside the image (the conv's zero padding drops the rest)
+// One workgroup per image owns its 3 x hin x win outputs: no float atomics, the same bits on every run.  A thread walks the
+// pixels p = tid, tid + 256, ..; it reads each dz pixel once (64 channels = four 64-B CB16 lines, as 16-B loads), the
+// 27 x 64 weights are wave-uniform loads (scalar cache), and the bilinear adjoint is two small contractions against per-row /
+// per-column tap tables in LDS: tab[r][k][i] = weight of taxel i in upsampled row r + k - 1 (0 outside the image; clamped
+// edge taps add up).  Per-thread partials meet through a fixed shuffle tree and a fixed-order sum over the 4 waves.
+// ------------------------------------------------------------------------------------------
+#define STEM_DG_MAXT 4     // taxels per axis (TactileSR: 4 x 4)
+
+template <bool B16>
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const float* __restrict__ w, const float* __restrict__ dz,
+                                                         int dz_ctot, int dz_coff, int hin, int win, int sf,
+                                                         float* __restrict__ dx, int dx_ctot, int dx_coff, int accumulate) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int H = hin * sf, W = win * sf, HW = H * W;
+  float* taby = smem;                                  // [H][3][4]
+  float* tabx = smem + H * 12;                         // [W][3][4]
+  float* red = tabx + W * 12;                          // [4 waves][48]
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const float sc = 1.0f / (float)sf;
+  for (int e = tid; e < (H + W) * 3; e += 256) {
+    const bool isy = e < H * 3;
+    const int k = isy ? e : e - H * 3;
+    const int r = k / 3, kk = k - r * 3, n = isy ? H : W, nin = isy ? hin : win;
+    const int q = r + kk - 1;
+    float v[STEM_DG_MAXT] = {0.f, 0.f, 0.f, 0.f};
+    if (q >= 0 && q < n) {
+      int i0, i1; float lam;
+      bilin_src_t(q, sc, nin, i0, i1, lam);
+#pragma unroll
+      for (int i = 0; i < STEM_DG_MAXT; ++i) v[i] = (i == i0 ? 1.f - lam : 0.f) + (i == i1 ? lam : 0.f);
+    }
+    *(f32x4*)((isy ? taby : tabx) + k * 4) = (f32x4){v[0], v[1], v[2], v[3]};
+  }
+  __syncthreads();
+  float acc[3][STEM_DG_MAXT][STEM_DG_MAXT];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int i = 0; i < STEM_DG_MAXT; ++i)
+#pragma unroll
+      for (int j = 0; j < STEM_DG_MAXT; ++j) acc[c][i][j] = 0.f;
+  const size_t plane = (size_t)HW * 16;
+  const size_t base = ((size_t)b * (dz_ctot >> 4) + (dz_coff >> 4)) * plane;
+  for (int p = tid; p < HW; p += 256) {
+    float d[64];
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const f32x4 v = tsr_ld4<B16>(dz, base + blk * plane + (size_t)p * 16 + q4 * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[blk * 16 + q4 * 4 + e] = v[e];
+      }
+    float t[27];
+#pragma unroll
+    for (int r = 0; r < 27; ++r) t[r] = 0.f;
+#pragma unroll
+    for (int co = 0; co < 64; co += 2) {
+      // the weights come through the scalar cache, two rows per step: the empty asm keeps the compiler from hoisting all
+      // 1728 uniform loads out of the pixel loop (they would not fit in SGPRs and spill)
+      int wo = co * 27;
+      asm volatile("" : "+s"(wo));
+      const float* wr = w + wo;
+#pragma unroll
+      for (int r = 0; r < 27; ++r) t[r] = fmaf(wr[27 + r], d[co + 1], fmaf(wr[r], d[co], t[r]));
+    }
+    const int y = p / W, x = p - y * W;
+    f32x4 ty[3], tx[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      ty[k] = *(const f32x4*)(taby + (y * 3 + k) * 4);
+      tx[k] = *(const f32x4*)(tabx + (x * 3 + k) * 4);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh) {
+        float u[STEM_DG_MAXT];                         // u[j] = sum_kw A_x(x + kw - 1, j) t[c][kh][kw]
+#pragma unroll
+        for (int j = 0; j < STEM_DG_MAXT; ++j)
+          u[j] = fmaf(tx[2][j], t[c * 9 + kh * 3 + 2], fmaf(tx[1][j], t[c * 9 + kh * 3 + 1], tx[0][j] * t[c * 9 + kh * 3]));
+#pragma unroll
+        for (int i = 0; i < STEM_DG_MAXT; ++i)
+#pragma unroll
+          for (int j = 0; j < STEM_DG_MAXT; ++j) acc[c][i][j] = fmaf(ty[kh][i], u[j], acc[c][i][j]);
+      }
+  }
+  // fixed-order reduction: butterfly within the wave, then the 4 wave partials in wave order
+  const int lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int i = 0; i < STEM_DG_MAXT; ++i)
+#pragma unroll
+      for (int j = 0; j < STEM_DG_MAXT; ++j) {
+        float v = acc[c][i][j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) red[wv * 48 + (c * STEM_DG_MAXT + i) * STEM_DG_MAXT + j] = v;
+      }
+  __syncthreads();
+  if (tid < 48) {
+    const int c = tid / 16, i = (tid >> 2) & 3, j = tid & 3;
+    if (i < hin && j < win) {
+      const float v = (red[tid] + red[48 + tid]) + (red[96 + tid] + red[144 + tid]);
+      float* o = dx + (((size_t)b * dx_ctot + dx_coff + c) * hin + i) * win + j;
+      *o = accumulate ? *o + v : v;
+    }
+  }
+}
+
+static int stem_dgrad_impl(const float* w_oihw, const float* dz, int dz_ctot, int dz_coff, int hin, int win, int sf,
+                           float* dx, int dx_ctot, int dx_coff, int accumulate, int B, void* stream, bool b16) {
+  if (!w_oihw || !dz || !dx || B <= 0 || hin <= 0 || win <= 0 || sf <= 0 || hin > STEM_DG_MAXT || win > STEM_DG_MAXT ||
+      (dz_ctot & 15) || (dz_coff & 15) || dz_coff < 0 || dz_coff + 64 > dz_ctot || dx_coff < 0 || dx_coff + 3 > dx_ctot ||
+      (accumulate != 0 && accumulate != 1))
+    return TSR_ERR_ARG;
+  const size_t fl = (size_t)(hin + win) * sf * 12 + 4 * 48;
+  if (fl * 4 > 64 * 1024) return TSR_ERR_ARG;
+  if (b16)
+    hipLaunchKernelGGL(stem_dgrad_kernel<true>, dim3(B), dim3(256), fl * 4, (hipStream_t)stream, w_oihw, dz, dz_ctot,
+                       dz_coff, hin, win, sf, dx, dx_ctot, dx_coff, accumulate);
+  else
+    hipLaunchKernelGGL(stem_dgrad_kernel<false>, dim3(B), dim3(256), fl * 4, (hipStream_t)stream, w_oihw, dz, dz_ctot,
+                       dz_coff, hin, win, sf, dx, dx_ctot, dx_coff, accumulate);
+  return tsr_check_launch();
+}
+
+extern "C" int tsr_stem_dgrad(const float* w_oihw, const float* dz, int dz_ctot, int dz_coff, int hin, int win, int sf,
+                              float* dx, int dx_ctot, int dx_coff, int accumulate, int B, void* stream) {
+  return stem_dgrad_impl(w_oihw, dz, dz_ctot, dz_coff, hin, win, sf, dx, dx_ctot, dx_coff, accumulate, B, stream, false);
+}
+
+// dz is a bf16 CB16 tensor (training with bf16 activation storage); fp32 arithmetic
+extern "C" int tsr_stem_dgrad_b16(const float* w_oihw, const void* dz, int dz_ctot, int dz_coff, int hin, int win, int sf,
+                                  float* dx, int dx_ctot, int dx_coff, int accumulate, int B, void* stream) {
+  return stem_dgrad_impl(w_oihw, (const float*)dz, dz_ctot, dz_coff, hin, win, sf, dx, dx_ctot, dx_coff, accumulate, B,
+                         stream, true);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -401,7 +401,8 @@ class TrainEngine:
         H, W = hin * sf, win * sf
         HW = H * W
         c = self._new_ctx(B, H, W, dev)
-        c.x, c.hin, c.win = x, hin, win
+        c.x, c.hin, c.win = x.detach(), hin, win
+        c.want_dx = False        # TactileSRTrainFn sets it when the taxels require grad: backward then also returns dx
         st_entries = c.st_entries
 
         def buf(ch):
@@ -680,6 +681,9 @@ class TrainEngine:
 
         new_amax = self._amax_pool(c, dev)      # a gradient tensor consumed by an MFMA launch carries max|.|
         dout = dout.contiguous().float()
+        # taxel gradient (only when the input requires grad): frame 0 gets the force stem's store, then its pattern stem's add
+        dx = torch.empty(c.x.shape, dtype=torch.float32, device=dev) if c.want_dx else None
+        c.dx = dx
         # ---- head: out = relu(conv(h0)), h0 = relu(conv(hcat))
         ns = max(1, min(B * (8 if H > 64 else 1), 2048))     # (image split, row band) entries: ~8 resident workgroups per CU
         dz_h0 = buf(128)
@@ -719,6 +723,8 @@ class TrainEngine:
         gw = grads.dest("input_layer_force.1.weight", m.input_layer_force[1].weight.shape)
         call("tsr_reduce_splits", ptr(sslab), ptr(gw), _L(64 * 27), _I(ns), _F(1.0), stream())
         grads.put("input_layer_force.1.weight", gw)
+        if dx is not None:
+            self._stem_dgrad(c, m.input_layer_force[1].weight, dpre.buf, dpre.ctot, dpre.coff, dx, 0, 0)
 
         # ---- pattern branch: MSRB blocks reversed
         dpre = Act(g_hcat, 128, 64, 64, amax=am_ghcat)
@@ -756,7 +762,15 @@ class TrainEngine:
             gw = grads.dest(name + ".1.weight", seq[1].weight.shape)
             call("tsr_reduce_splits", ptr(sslab), ptr(gw), _L(64 * 27), _I(ns), _F(1.0), stream())
             grads.put(name + ".1.weight", gw)
+            if dx is not None:
+                self._stem_dgrad(c, seq[1].weight, g1, 64, 0, dx, m.axisCnt * t, int(t == 0))
         return grads.finalize()
+
+    def _stem_dgrad(self, c, weight, dz, dz_ctot, dz_coff, dx, dx_coff, accumulate):
+        """dx[:, dx_coff:dx_coff+3] (=|+=) the taxel gradient of one stem (bilinear x sf + conv 3 -> 64) given its dz."""
+        call("tsr_stem_dgrad_b16" if self.io16 else "tsr_stem_dgrad", ptr(weight.detach().contiguous()), ptr(dz),
+             _I(dz_ctot), _I(dz_coff), _I(c.hin), _I(c.win), _I(self.m.scale_factor), ptr(dx), _I(dx.shape[1]),
+             _I(dx_coff), _I(accumulate), _I(c.B), stream())
 
 
 class TactileSRTrainFn(torch.autograd.Function):
@@ -766,6 +780,7 @@ class TactileSRTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, engine: TrainEngine, names, x, *params):
         out, c = engine.forward(x)
+        c.want_dx = bool(ctx.needs_input_grad[2])      # d loss / d taxels only when the caller's input requires grad
         ctx.engine, ctx.c, ctx.names = engine, c, names
         if any(ctx.needs_input_grad):
             from ..ddp import note_forward
@@ -774,12 +789,14 @@ class TactileSRTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        grads = ctx.engine.backward(ctx.c, dout)
+        c = ctx.c
+        grads = ctx.engine.backward(c, dout)
+        dx, c.dx = c.dx, None
         ctx.c = None
         missing = [n for n in ctx.names if n not in grads]
         if missing:
             raise _lib.TactileSRHipError(f"backward produced no gradient for {missing[:4]}...")
-        return (None, None, None) + tuple(grads[n] for n in ctx.names)
+        return (None, None, dx) + tuple(grads[n] for n in ctx.names)
 
 
 class BlockEngine(TrainEngine):

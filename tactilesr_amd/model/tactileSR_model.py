@@ -660,8 +660,9 @@ class TactileSR(nn.Module):
             # batch-statistics BatchNorm + autograd through the HIP backward (model/_train.py)
             from ._train import TactileSRTrainFn
             named = list(self.named_parameters())
+            # (not detached: with LR.requires_grad_() autograd routes d loss / d taxels back through .float() / slicing)
             out = TactileSRTrainFn.apply(self.train_engine(), [n for n, _ in named],
-                                         x.detach().float().contiguous(), *[p for _, p in named])
+                                         x.float().contiguous(), *[p for _, p in named])
             self._plan = None      # running statistics were updated in place by the kernels
             return out
         x = x.detach().float().contiguous()
