@@ -310,7 +310,10 @@ int tsr_bn_bwd_apply(float* g, int g_ctot, int g_coff, const float* z, int z_cto
                      const float* c1, const float* c2, const float* c3, int C, int B, int HW,
                      float* out_amax /* optional: max|g| after the update */, void* stream);
 
-/* Backward of tsr_stem_fwd's conv weight: slab[s][64][3][3][3] partials (the taxel gradient is tsr_stem_dgrad). */
+/* Backward of tsr_stem_fwd's conv weight: slab[s][64][3][3][3] partials, s < nsplit, any nsplit >= 1 (the taxel gradient is
+ * tsr_stem_dgrad).  Tall images are cut into row bands so that one band (+ halo) of the upsampled image fits in LDS: the
+ * bands are spread over the splits as far as they divide nsplit, a workgroup walks the rest; status 1 only when three
+ * padded rows of 3 x (W + 2) floats plus the taxels exceed 160 KB (no TactileSR shape). */
 int tsr_stem_wgrad(const float* lr, int lr_ctot, int lr_coff, int hin, int win, int sf,
                    const float* dz, int dz_ctot, int dz_coff, float* slab, int nsplit, int B, void* stream);
 /* Taxel gradient of the stem (reference model/tactileSR_model.py:35-37,60-61: Upsample(bilinear, align_corners=False) +
@@ -321,7 +324,9 @@ int tsr_stem_wgrad(const float* lr, int lr_ctot, int lr_coff, int hin, int win, 
 int tsr_stem_dgrad(const float* w_oihw, const float* dz, int dz_ctot, int dz_coff, int hin, int win, int sf,
                    float* dx, int dx_ctot, int dx_coff, int accumulate, int B, void* stream);
 /* Backward of tsr_head_fwd: dz_h0 = dgrad(dout*[out>0]) * [h0>0] (CB16) and weight partials
- * wslab[s][cin][3][3]. */
+ * wslab[s][cin][3][3].  The weight gradient holds the zero-padded H x W image in 64 KB of LDS: (H + 2)(W + 2) <= 16384,
+ * i.e. at most 126 x 126 -- TactileSR trains at scale_factor <= 31 on 4 x 4 taxels.  Larger shapes return 1 before any
+ * launch (dz_h0, wslab and dz_amax untouched). */
 int tsr_head_bwd(const float* dout, const float* out, const float* h0, int h_ctot, int cin,
                  const float* w_oihw, float* dz_h0, int dz_ctot, float* wslab, int nsplit,
                  int B, int H, int W, float* dz_amax /* optional: max|dz_h0| */, void* stream);

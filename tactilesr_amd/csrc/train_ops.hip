@@ -235,19 +235,18 @@ __device__ __forceinline__ void bilin_src_t(int dst, float scale, int n_in, int&
   lam = src - (float)i0;
 }
 
-// one workgroup per (image split, band of rows); thread = (co = tid&63, pixel phase = tid>>6).  `bands` > 1 for tall images:
-// a workgroup then holds only its band of the upsampled image (+ one halo row each side) in LDS -- at 100 x 100 the whole
-// image is 125 KB, i.e. one workgroup per CU -- and the slab entries are (band, image split) pairs, nsplit in all.
+// one workgroup per (image split, band group); thread = (co = tid&63, pixel phase = tid>>6).  `bands` > 1 for tall images:
+// a workgroup then holds only one band of the upsampled image (+ one halo row each side) in LDS at a time -- at 100 x 100 the
+// whole image is 125 KB, i.e. one workgroup per CU.  The slab entries are (band group, image split) pairs, nsplit in all:
+// gridDim.y band groups (a divisor of nsplit), a workgroup walks the bands blockIdx.y, blockIdx.y + gridDim.y, .. of its images.
 template <bool B16>
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ lr, int lr_ctot, int lr_coff,
                                                          int hin, int win, int sf, const float* __restrict__ dz,
                                                          int dz_ctot, int dz_coff, float* __restrict__ slab, int B,
-                                                         int nsplit, int bands) {
+                                                         int bands) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int Himg = hin * sf, W = win * sf, WP = W + 2;
   const int RBAND = (Himg + bands - 1) / bands;
-  const int yb0 = blockIdx.y * RBAND;
-  const int H = Himg - yb0 < RBAND ? Himg - yb0 : RBAND;      // rows of this band
   const int HP = RBAND + 2;
   float* tax = smem;                                   // [3][hin*win]
   float* up = smem + ((3 * hin * win + 3) & ~3);       // [3][HP][WP] zero padded: band rows yb0 - 1 .. yb0 + RBAND
@@ -259,57 +258,60 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
   for (int k = 0; k < 27; ++k) acc[k] = 0.f;
   const float sc = 1.0f / (float)sf;
   const int oc = dz_coff + co;
-  nsplit /= bands;                                     // image splits
-  for (int b = blockIdx.x; b < B; b += nsplit) {
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
     __syncthreads();
     for (int i = tid; i < 3 * hin * win; i += 256) tax[i] = lr[((size_t)b * lr_ctot + lr_coff) * hin * win + i];
-    __syncthreads();
-    for (int i = tid; i < 3 * HP * WP; i += 256) {
-      const int c = i / (HP * WP), rem = i - c * (HP * WP);
-      const int gy = yb0 + rem / WP - 1, gx = rem % WP - 1;
-      float v = 0.f;
-      if (gy >= 0 && gy < Himg && gx >= 0 && gx < W) {
-        int ya, yb, xa, xb; float ly, lx;
-        bilin_src_t(gy, sc, hin, ya, yb, ly);
-        bilin_src_t(gx, sc, win, xa, xb, lx);
-        const float* t = tax + c * hin * win;
-        const float top = (1.f - lx) * t[ya * win + xa] + lx * t[ya * win + xb];
-        const float bot = (1.f - lx) * t[yb * win + xa] + lx * t[yb * win + xb];
-        v = (1.f - ly) * top + ly * bot;
-      }
-      up[i] = v;
-    }
-    __syncthreads();
-    const size_t dzo = (((size_t)b * (dz_ctot >> 4) + (oc >> 4)) * HW) * 16 + (oc & 15);
-    // A wave walks whole rows (y = ph, ph + 4, ..) in chunks of PU pixels.  The PU gradient loads of a chunk are requested
-    // together (one dependent 2- / 4-byte load per pixel made the loop a chain of memory latencies: 0.78 ms per launch at
-    // B = 2048 for 0.42 GB), and the 3x3x3 window of the upsampled image slides in registers: column x + 3 replaces column x
-    // (9 LDS reads per pixel instead of 27; the reads are broadcasts -- all 64 lanes of a wave share the pixel).
-    constexpr int PU = 8;
-    for (int y = ph; y < H; y += 4) {
-      for (int x0 = 0; x0 < W; x0 += PU) {
-        float d[PU];
-#pragma unroll
-        for (int u = 0; u < PU; ++u) {
-          const int x = x0 + u;
-          const float v = tsr_ld1<B16>(dz, dzo + (size_t)((yb0 + y) * W + (x < W ? x : x0)) * 16);
-          d[u] = x < W ? v : 0.f;                  // (a chunk's tail beyond the row adds nothing; its window reads stay in the padding)
+    for (int bd = blockIdx.y; bd < bands; bd += gridDim.y) {
+      const int yb0 = bd * RBAND;
+      const int H = Himg - yb0 < RBAND ? Himg - yb0 : RBAND;      // rows of this band
+      __syncthreads();
+      for (int i = tid; i < 3 * HP * WP; i += 256) {
+        const int c = i / (HP * WP), rem = i - c * (HP * WP);
+        const int gy = yb0 + rem / WP - 1, gx = rem % WP - 1;
+        float v = 0.f;
+        if (gy >= 0 && gy < Himg && gx >= 0 && gx < W) {
+          int ya, yb, xa, xb; float ly, lx;
+          bilin_src_t(gy, sc, hin, ya, yb, ly);
+          bilin_src_t(gx, sc, win, xa, xb, lx);
+          const float* t = tax + c * hin * win;
+          const float top = (1.f - lx) * t[ya * win + xa] + lx * t[ya * win + xb];
+          const float bot = (1.f - lx) * t[yb * win + xa] + lx * t[yb * win + xb];
+          v = (1.f - ly) * top + ly * bot;
         }
-        float col[3][9];                           // col[(x - x0) % 3][c * 3 + kh] = up[c][y + kh][x]
+        up[i] = v;
+      }
+      __syncthreads();
+      const size_t dzo = (((size_t)b * (dz_ctot >> 4) + (oc >> 4)) * HW) * 16 + (oc & 15);
+      // A wave walks whole rows (y = ph, ph + 4, ..) in chunks of PU pixels.  The PU gradient loads of a chunk are requested
+      // together (one dependent 2- / 4-byte load per pixel made the loop a chain of memory latencies: 0.78 ms per launch at
+      // B = 2048 for 0.42 GB), and the 3x3x3 window of the upsampled image slides in registers: column x + 3 replaces column x
+      // (9 LDS reads per pixel instead of 27; the reads are broadcasts -- all 64 lanes of a wave share the pixel).
+      constexpr int PU = 8;
+      for (int y = ph; y < H; y += 4) {
+        for (int x0 = 0; x0 < W; x0 += PU) {
+          float d[PU];
 #pragma unroll
-        for (int j = 0; j < 3; ++j)
+          for (int u = 0; u < PU; ++u) {
+            const int x = x0 + u;
+            const float v = tsr_ld1<B16>(dz, dzo + (size_t)((yb0 + y) * W + (x < W ? x : x0)) * 16);
+            d[u] = x < W ? v : 0.f;                  // (a chunk's tail beyond the row adds nothing; its window reads stay in the padding)
+          }
+          float col[3][9];                           // col[(x - x0) % 3][c * 3 + kh] = up[c][y + kh][x]
 #pragma unroll
-          for (int r = 0; r < 9; ++r) col[j][r] = up[((r / 3) * HP + y + (r % 3)) * WP + x0 + j];
+          for (int j = 0; j < 3; ++j)
 #pragma unroll
-        for (int u = 0; u < PU; ++u) {
+            for (int r = 0; r < 9; ++r) col[j][r] = up[((r / 3) * HP + y + (r % 3)) * WP + x0 + j];
 #pragma unroll
-          for (int r = 0; r < 9; ++r)
+          for (int u = 0; u < PU; ++u) {
 #pragma unroll
-            for (int kw = 0; kw < 3; ++kw) acc[r * 3 + kw] = fmaf(d[u], col[(u + kw) % 3][r], acc[r * 3 + kw]);
-          if (u + 1 < PU) {
-            const int xn = x0 + u + 3 < WP ? x0 + u + 3 : WP - 1;          // (past the padded row only under a zero gradient)
+            for (int r = 0; r < 9; ++r)
 #pragma unroll
-            for (int r = 0; r < 9; ++r) col[u % 3][r] = up[((r / 3) * HP + y + (r % 3)) * WP + xn];
+              for (int kw = 0; kw < 3; ++kw) acc[r * 3 + kw] = fmaf(d[u], col[(u + kw) % 3][r], acc[r * 3 + kw]);
+            if (u + 1 < PU) {
+              const int xn = x0 + u + 3 < WP ? x0 + u + 3 : WP - 1;          // (past the padded row only under a zero gradient)
+#pragma unroll
+              for (int r = 0; r < 9; ++r) col[u % 3][r] = up[((r / 3) * HP + y + (r % 3)) * WP + xn];
+            }
           }
         }
       }
@@ -322,7 +324,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
   for (int k = 0; k < 27; ++k) red[(ph * 64 + co) * 27 + k] = acc[k];
   __syncthreads();
   for (int i = tid; i < 64 * 27; i += 256)
-    slab[((size_t)blockIdx.y * nsplit + blockIdx.x) * 64 * 27 + i] =
+    slab[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 64 * 27 + i] =
         (red[i] + red[64 * 27 + i]) + (red[2 * 64 * 27 + i] + red[3 * 64 * 27 + i]);
 }
 
@@ -332,13 +334,19 @@ static int stem_wgrad_impl(const float* lr, int lr_ctot, int lr_coff, int hin, i
   if (!lr || !dz || !slab || nsplit <= 0 || B <= 0 || (dz_ctot & 15) || (dz_coff & 15) || dz_coff + 64 > dz_ctot)
     return TSR_ERR_ARG;
   const int H = hin * sf, W = win * sf;
-  // bands of rows per image: the band (+ halo) within 32 KB of LDS, if the splits divide (slab entries = nsplit either way)
-  int bands = 1;
-  while (bands < 8 && (size_t)3 * ((H + bands - 1) / bands + 2) * (W + 2) * 4 > 32 * 1024 && nsplit % (2 * bands) == 0 &&
-         nsplit / (2 * bands) >= 1)
-    bands *= 2;
-  size_t fl = ((3 * hin * win + 3) & ~3) + (size_t)3 * ((H + bands - 1) / bands + 2) * (W + 2);
-  if (fl < 4 * 64 * 27) fl = 4 * 64 * 27;
+  if (hin <= 0 || win <= 0 || sf <= 0) return TSR_ERR_ARG;
+  // LDS floats of a workgroup that holds `bands` bands of rows per image (one at a time, + halo rows)
+  auto lds_floats = [&](int bands) {
+    const size_t fl = ((3 * hin * win + 3) & ~3) + (size_t)3 * ((H + bands - 1) / bands + 2) * (W + 2);
+    return fl < 4 * 64 * 27 ? (size_t)4 * 64 * 27 : fl;
+  };
+  // band groups across the grid: the band (+ halo) within 32 KB of LDS, as far as they divide the splits (slab entries =
+  // nsplit either way); then bands per image, a multiple of the groups, until the band fits the 160 KB LDS at all
+  int groups = 1;
+  while (groups < 8 && lds_floats(groups) * 4 > 32 * 1024 && nsplit % (2 * groups) == 0) groups *= 2;
+  int bands = groups;
+  while (bands < H && lds_floats(bands) * 4 > 160 * 1024) bands *= 2;
+  const size_t fl = lds_floats(bands);
   if (fl * 4 > 160 * 1024) return TSR_ERR_ARG;
   static bool attr_set = false;
   if (!attr_set) {
@@ -347,11 +355,11 @@ static int stem_wgrad_impl(const float* lr, int lr_ctot, int lr_coff, int hin, i
     attr_set = true;
   }
   if (b16)
-    hipLaunchKernelGGL(stem_wgrad_kernel<true>, dim3(nsplit / bands, bands), dim3(256), fl * 4, (hipStream_t)stream, lr, lr_ctot,
-                       lr_coff, hin, win, sf, dz, dz_ctot, dz_coff, slab, B, nsplit, bands);
+    hipLaunchKernelGGL(stem_wgrad_kernel<true>, dim3(nsplit / groups, groups), dim3(256), fl * 4, (hipStream_t)stream, lr, lr_ctot,
+                       lr_coff, hin, win, sf, dz, dz_ctot, dz_coff, slab, B, bands);
   else
-    hipLaunchKernelGGL(stem_wgrad_kernel<false>, dim3(nsplit / bands, bands), dim3(256), fl * 4, (hipStream_t)stream, lr, lr_ctot,
-                       lr_coff, hin, win, sf, dz, dz_ctot, dz_coff, slab, B, nsplit, bands);
+    hipLaunchKernelGGL(stem_wgrad_kernel<false>, dim3(nsplit / groups, groups), dim3(256), fl * 4, (hipStream_t)stream, lr, lr_ctot,
+                       lr_coff, hin, win, sf, dz, dz_ctot, dz_coff, slab, B, bands);
   return tsr_check_launch();
 }
 
@@ -658,16 +666,18 @@ static int head_bwd_impl(const float* dout, const float* out, const float* h0, i
                          const float* w_oihw, float* dz_h0, int dz_ctot, float* wslab, int nsplit,
                          int B, int H, int W, float* dz_amax, void* stream) {
   if (!dout || !out || !h0 || !w_oihw || !dz_h0 || !wslab || nsplit <= 0 || (cin & 15) || cin > 256 || cin > h_ctot ||
-      cin > dz_ctot || (h_ctot & 15) || (dz_ctot & 15))
+      cin > dz_ctot || (h_ctot & 15) || (dz_ctot & 15) || B <= 0 || H <= 0 || W <= 0)
     return TSR_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int items = H * W * 4;
-  hipLaunchKernelGGL(head_bwd_kernel<B16>, dim3((items + 255) / 256, B), dim3(256), (size_t)9 * cin * 4, st, dout, out,
-                     h0, h_ctot, cin, w_oihw, dz_h0, dz_ctot, B, H, W, dz_amax);
+  // head_wgrad_kernel keeps the whole zero-padded masked dout image in LDS: (H + 2)(W + 2) floats within 64 KB, i.e. at most
+  // 126 x 126 (4 x 4 taxels: scale_factor <= 31).  Checked before the first launch: a refused call writes nothing.
   size_t fl = (size_t)(H + 2) * (W + 2);
   const size_t redf = (size_t)(256 / cin) * cin * 9;
   if (fl < redf) fl = redf;
   if (fl * 4 > 64 * 1024) return TSR_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int items = H * W * 4;
+  hipLaunchKernelGGL(head_bwd_kernel<B16>, dim3((items + 255) / 256, B), dim3(256), (size_t)9 * cin * 4, st, dout, out,
+                     h0, h_ctot, cin, w_oihw, dz_h0, dz_ctot, B, H, W, dz_amax);
   hipLaunchKernelGGL(head_wgrad_kernel<B16>, dim3(nsplit), dim3(256), fl * 4, st, dout, out, h0, h_ctot, cin, wslab, B, H,
                      W, nsplit);
   return tsr_check_launch();

@@ -23,6 +23,18 @@ from .._lib import call, ptr, stream
 _I, _F, _D, _L = c_int, c_float, c_double, c_longlong
 
 
+# tsr_head_bwd keeps the zero-padded H x W head gradient in 64 KB of LDS: outputs up to 126 x 126 (4 x 4 taxels: sf <= 31)
+HEAD_BWD_LDS_BYTES = 64 * 1024
+
+
+def check_trainable_size(H, W):
+    """Raise before the train step launches anything when its H x W output is beyond the library's train kernels."""
+    if (H + 2) * (W + 2) * 4 > HEAD_BWD_LDS_BYTES:
+        raise _lib.TactileSRHipError(
+            f"train step at {H}x{W} output: tsr_head_bwd needs (H+2)*(W+2)*4 <= {HEAD_BWD_LDS_BYTES} bytes of LDS "
+            f"(at most 126x126, scale_factor <= 31 on 4x4 taxels)")
+
+
 class ConvDesc(ctypes.Structure):
     """Mirror of ``tsr_conv_desc`` (include/tactilesr_hip.h)."""
     _fields_ = [
@@ -400,6 +412,7 @@ class TrainEngine:
         sf, T, A = m.scale_factor, m.seqsCnt, m.axisCnt
         H, W = hin * sf, win * sf
         HW = H * W
+        check_trainable_size(H, W)          # before any launch: a refused step leaves parameters and statistics as they were
         c = self._new_ctx(B, H, W, dev)
         c.x, c.hin, c.win = x.detach(), hin, win
         c.want_dx = False        # TactileSRTrainFn sets it when the taxels require grad: backward then also returns dx

@@ -532,30 +532,7 @@ def test_train_multiframe_and_odd_batch_vs_oracle(T, Tn, nm, B, sf):
 
 
 def _train_step_vs_oracle(T, cfg, B, seed, tol=1e-5, loss_tol=1e-5):
-    sf, Tn = cfg.get("scale_factor", 10), cfg.get("seqsCnt", 1)
-    sd = O.random_state_dict(O.tactilesr_state_shapes(**cfg), seed)
-    g = torch.Generator().manual_seed(seed + 1)
-    LR = torch.rand(B, 3 * Tn, 4, 4, generator=g) * 8
-    HR = torch.rand(B, 1, 4 * sf, 4 * sf, generator=g) * 25
-    l64, _, ns64, pre64 = GC.oracle_grads(sd, LR, HR, scale_factor=sf, record=True)
-    m = T.TactileSR(**cfg)
-    m.load_state_dict(sd, strict=True)
-    m = m.cuda().train()
-    eng = _debug_engine(m)
-    out = m(LR.cuda())
-    loss = F.mse_loss(out, HR.cuda())
-    assert abs(loss.item() - l64) < loss_tol * abs(l64)
-    loss.backward()
-    new_sd = m.state_dict()
-    for k, v in ns64.items():
-        if k.endswith("running_mean") or k.endswith("running_var"):
-            assert relerr(new_sd[k], v) < 1e-5, k
-    masks = {k: v.cpu() for k, v in eng.activation_masks(eng.last_ctx).items()}
-    flips = GC.check_pattern(masks, pre64)
-    _, g64m, _, _ = GC.oracle_grads(sd, LR, HR, scale_factor=sf, masks=masks)
-    worst = GC.check_grads({k: p.grad for k, p in m.named_parameters()}, g64m, tol=tol)
-    print(f"[train-vs-oracle {cfg} B={B}] {flips} ReLU flips; worst on-pattern grad error {worst[0]:.2e} ({worst[1]})")
-    return m
+    return GC.train_step_vs_oracle(T, cfg, B, seed, tol=tol, loss_tol=loss_tol)[0]
 
 
 def test_train_step_distinct_frames_wide_amplitude_vs_oracle(T):
@@ -827,17 +804,7 @@ def test_seqs_bf16_storage_train_step_B256_full_size_tiling_invariance(T):
     torch.cuda.empty_cache()
 
 
-def _emulated_step(sd, LR, HR, **kw):
-    """Loss, gradients and new running statistics of the oracle's bf16-emulating train forward (`emulate="bf16"`)."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in sd.items() if O.is_trainable(k)}
-    full = dict(sd)
-    full.update(leaves)
-    ns = {}
-    out = O.tactilesr_forward(full, LR, training=True, new_stats=ns, emulate="bf16", **kw)
-    loss = F.mse_loss(out, HR)
-    gl = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
-    grads = {k: (g if g is not None else torch.zeros_like(leaves[k])) for k, g in zip(leaves, gl)}
-    return float(loss), grads, ns, out.detach()
+_emulated_step = GC.emulated_step
 
 
 @pytest.mark.parametrize("cfg,B,seed", [(dict(patternFeatureExtraLayerCnt=2), 4, 211),
@@ -856,41 +823,7 @@ def test_train_step_bf16_storage_vs_bf16_emulating_oracle(T, cfg, B, seed):
     of the kernels: seeds 977 / 978 / 979 give 0.9946 / 0.9981 / 0.9690 on the LDS-DMA kernels and 0.9961 / 0.9980 / 0.9642 on the
     32x32x16 kernels they replaced (tools/bf16_grad_cosine_probe.py); at B = 11: 0.9982 / 0.9991 / 0.9877 against 0.9985 /
     0.9990 / 0.9852."""
-    sf, Tn = cfg.get("scale_factor", 10), cfg.get("seqsCnt", 1)
-    sd = O.random_state_dict(O.tactilesr_state_shapes(**cfg), seed)
-    g = torch.Generator().manual_seed(seed + 1)
-    LR = torch.rand(B, 3 * Tn, 4, 4, generator=g) * 8
-    HR = torch.rand(B, 1, 4 * sf, 4 * sf, generator=g) * 25
-    l_e, g_e, ns_e, out_e = _emulated_step(sd, LR, HR, scale_factor=sf)
-    m = T.TactileSR(**cfg)
-    m.train_impl = "bf16"            # explicit arithmetic choice (no environment switch)
-    m.load_state_dict(sd, strict=True)
-    m = m.cuda().train()
-    eng = _debug_engine(m)
-    assert eng.io16 and eng.act_dtype == torch.bfloat16
-    out = m(LR.cuda())
-    ctx = eng.last_ctx
-    assert all(t.dtype == torch.bfloat16 for t in (ctx.hcat, ctx.h0, ctx.zf, ctx.catT, ctx.blocks[0].cat1, ctx.blocks[0].cat2))
-    loss = F.mse_loss(out, HR.cuda())
-    e_out = relerr(out, out_e)
-    assert e_out <= 2.0 ** -6 and abs(loss.item() - l_e) <= 2e-3 * abs(l_e), (e_out, loss.item(), l_e)
-    loss.backward()
-    new_sd = m.state_dict()
-    for k, v in ns_e.items():
-        if k.endswith("running_mean") or k.endswith("running_var"):
-            assert relerr(new_sd[k], v) < 2e-3, k
-    worst = 1.0
-    for k, p in m.named_parameters():
-        ref = g_e[k].double().flatten()
-        got = p.grad.detach().cpu().double().flatten()
-        if float(ref.abs().max()) < 1e-6 * float(max(v.abs().max() for v in g_e.values())):
-            continue                                    # conv bias in front of a train-mode BN: gradient == 0 + noise
-        cos = float(got @ ref / (got.norm() * ref.norm()).clamp_min(1e-30))
-        worst = min(worst, cos)
-        assert cos >= 0.995, (k, cos)
-        assert abs(float(got.norm() / ref.norm()) - 1.0) < 5e-2, (k, float(got.norm() / ref.norm()))
-    print(f"[bf16-storage train vs bf16 oracle {cfg} B={B}] out {e_out:.2e}, loss {abs(loss.item() - l_e) / abs(l_e):.2e}, "
-          f"worst gradient cosine {worst:.5f}")
+    GC.bf16_train_step_vs_emulating_oracle(T, cfg, B, seed)
 
 
 def test_bf16_storage_train_step_tiling_invariance(T):

@@ -53,3 +53,19 @@ def test_stem_dgrad_rejects_bad_arguments():
         assert call(hin=5) != 0 and call(win=0) != 0 and call(sf=0) != 0
         assert call(acc=2) != 0
         assert call(sf=2000) != 0               # tap tables beyond the LDS bound
+
+
+def test_stem_wgrad_and_head_bwd_refuse_oversize_shapes_before_any_launch():
+    """Shapes beyond the LDS bounds fail the host-side check (the fake pointers are never dereferenced): tsr_head_bwd at
+    128 x 128 (scale_factor 32 on 4 x 4 taxels; at most 126 x 126), tsr_stem_wgrad with a row too wide for 160 KB."""
+    lib = _lib.load()
+    fake, null = ctypes.c_void_p(16), ctypes.c_void_p(0)
+    amax = fake
+    for H in (128, 160):
+        assert lib.tsr_head_bwd(fake, fake, fake, 128, 128, fake, fake, 128, fake, 1, 1, H, H, amax, null) == 1
+        assert lib.tsr_head_bwd_b16(fake, fake, fake, 128, 128, fake, fake, 128, fake, 1, 1, H, H, null) == 1
+    for name in ("tsr_stem_wgrad", "tsr_stem_wgrad_b16"):
+        fn = getattr(lib, name)
+        assert fn(fake, 3, 0, 1, 4400, 1, fake, 64, 0, fake, 1, 1, null) == 1
+        assert fn(fake, 3, 0, 4, 4, 0, fake, 64, 0, fake, 1, 1, null) == 1          # sf 0
+        assert fn(fake, 3, 0, 4, 4, 10, fake, 64, 0, fake, 0, 1, null) == 1         # nsplit 0
