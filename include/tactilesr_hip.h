@@ -244,8 +244,11 @@ typedef struct tsr_conv_desc {
 int tsr_conv2d_ex(const tsr_conv_desc* desc, void* stream);
 int tsr_conv2d_slab_entries(int B, int H, int W);
 /* Entries the launch described by (cout, ks, nsplit) writes -- the count to hand to tsr_bn_stats_finalize /
- * tsr_bn_bwd_finalize (the fp16-split 3x3/5x5 kernels with 64 output channels use 4 images per workgroup, all other
- * forms 2: tsr_conv2d_slab_entries is the 2-image count).  Size slabs for the larger of the two. */
+ * tsr_bn_bwd_finalize: ceil(B / img) * tiles * img, tiles = ceil(H / 8) * ceil(W / 8), img = images per workgroup of the
+ * kernel that runs the launch -- 4 for the 3x3 / 5x5 launches of nsplit = -2 (fp16x3, both output widths) and of the
+ * one-plane bf16 forms (nsplit = 1, -1, and -3 / -4), 2 for every other form: tsr_conv2d_slab_entries is the 2-image count.
+ * Entry e = (image group * tiles + tile) * img + slot holds image group * img + slot; the slots of images >= B are written
+ * with count 0 (epi_mode 1) / zero sums (epi_mode 2).  Size slabs for the larger of the two. */
 int tsr_conv2d_slab_entries_ex(int B, int H, int W, int cout, int ks, int nsplit);
 
 /* Weights of the data-gradient convolution: W'[n][co][kh][kw] = W[co][ci0+n][K-1-kh][K-1-kw],

@@ -397,3 +397,23 @@ def test_seqs_index_table_follows_the_reference_arithmetic():
                     k += 1
         assert k == idx.shape[0]
     assert seqs_index_table()[0].shape == (18 * 9 * 16, 7)           # the shipped generator: 2592 items
+
+
+def test_conv_slab_entry_counts_follow_the_images_per_workgroup_of_each_form():
+    """include/tactilesr_hip.h: tsr_conv2d_slab_entries_ex = ceil(B / img) * tiles * img with img = 4 for the 3x3 / 5x5
+    launches of fp16x3 (-2) and of the one-plane bf16 forms (1, -1), 2 for every other form; tsr_conv2d_slab_entries is
+    the 2-image count.  Host arithmetic only: no device is touched."""
+    from tactilesr_amd import _lib
+    lib = _lib.load()
+    for B in (1, 2, 3, 4, 5, 70):
+        for H, W in ((40, 40), (13, 21), (9, 17), (5, 3), (1, 1), (12, 12)):
+            tiles = ((H + 7) // 8) * ((W + 7) // 8)
+            assert lib.tsr_conv2d_slab_entries(B, H, W) == ((B + 1) // 2) * tiles * 2
+            for ns in (0, 3, 2, 1, -1, -2):
+                for cout in (64, 128):
+                    for ks in (1, 3, 5):
+                        img = 4 if ks > 1 and ns in (-2, 1, -1) else 2
+                        got = lib.tsr_conv2d_slab_entries_ex(B, H, W, cout, ks, ns)
+                        assert got == ((B + img - 1) // img) * tiles * img, (B, H, W, cout, ks, ns, got)
+                        if img == 2:
+                            assert got == lib.tsr_conv2d_slab_entries(B, H, W)
