@@ -19,6 +19,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr, stream
+from .tactileSR_model import NS_F32, NS_F16X3, NS_B16, NS_B16K, NS_B16K_PAIR, _SlotPool, _timed, to_cb16, from_cb16
 
 _I, _F, _D, _L = c_int, c_float, c_double, c_longlong
 
@@ -99,9 +100,9 @@ def conv_ex(*, B, H, W, src: Act, w, cout, ks, out, out_ctot, out_coff, scale=No
 
 
 def _pack(w, cout, cin, ks, nsplit=0, w_amax=None):
-    if nsplit == -1:          # bf16 activation storage: the weights are the one-plane bf16 pack
+    if nsplit == NS_B16:      # bf16 activation storage: the weights are the one-plane bf16 pack
         nsplit = 1
-    if nsplit == -2:
+    if nsplit == NS_F16X3:
         n = _lib.load().tsr_conv_weight_bf16s_elems(cout, cin, ks, 2)
         wp = torch.empty(n, dtype=torch.float16, device=w.device)
         call("tsr_pack_conv_weight_f16s_dev", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), ptr(w_amax), stream())
@@ -117,13 +118,13 @@ def _pack(w, cout, cin, ks, nsplit=0, w_amax=None):
 
 
 def _pack_dgrad(w, cout, cin, ks, ci0, nprime, nsplit=0, w_amax=None):
-    if nsplit == -3:          # bf16 activation storage, the launch runs csrc/conv_b16k.hip: that kernel's slab layout
+    if nsplit == NS_B16K:     # bf16 activation storage, the launch runs csrc/conv_b16k.hip: that kernel's slab layout
         wp = torch.empty(_lib.load().tsr_conv_weight_b16k_elems(nprime, cout, ks), dtype=torch.bfloat16, device=w.device)
         call("tsr_pack_conv_weight_dgrad_b16k", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), _I(ci0), _I(nprime), stream())
         return wp
-    if nsplit == -1:
+    if nsplit == NS_B16:
         nsplit = 1
-    if nsplit == -2:
+    if nsplit == NS_F16X3:
         n = _lib.load().tsr_conv_weight_bf16s_elems(nprime, cout, ks, 2)
         wp = torch.empty(n, dtype=torch.float16, device=w.device)
         call("tsr_pack_conv_weight_dgrad_f16s_dev", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), _I(ci0), _I(nprime),
@@ -140,7 +141,7 @@ def _pack_dgrad(w, cout, cin, ks, ci0, nprime, nsplit=0, w_amax=None):
     return wp
 
 
-TRAIN_IMPLS = {"f32": 0, "bf16x6": 3, "fp16x3": -2, "bf16": -1, "bf16op": 1}
+TRAIN_IMPLS = {"f32": NS_F32, "bf16x6": 3, "fp16x3": NS_F16X3, "bf16": NS_B16, "bf16op": 1}
 
 
 class _Ctx:
@@ -163,37 +164,19 @@ class TrainEngine:
         self.n_buckets = 8
         self.profile = None      # bench.py: dict -> HIP-event brackets per launch family, on the launch stream
         # conv arithmetic of the train path (chosen EXPLICITLY: `TactileSR(train_impl=...)` / `model.train_impl = ...`;
-        # no environment variable changes it): 0 = fp32 MFMA, 3 = split-bf16 (six products, fp32-equivalent),
-        # -2 = two scaled fp16 planes (three products; operand scales from device-side max|.| scalars),
-        # -1 = "bf16": BASELINE's "bf16" configurations -- every stored activation / gradient tensor is bf16 CB16 (saved
+        # no environment variable changes it): "f32" = fp32 MFMA, "bf16x6" = split-bf16 (six products, fp32-equivalent),
+        # "fp16x3" = two scaled fp16 planes (three products; operand scales from device-side max|.| scalars),
+        # "bf16" = BASELINE's "bf16" configurations -- every stored activation / gradient tensor is bf16 CB16 (saved
         #      pre-activations z, dz, dgrad outputs), plain bf16 MFMA operands, fp32 accumulation, fp32 master weights,
         #      BatchNorm statistics, weight gradients and Adam (the reference's reduced-precision switch is the unused
-        #      fp16 autocast of cpu/trainer.py:96,203,346-362); 1 = "bf16op": bf16 operands on fp32 tensors (A/B only)
+        #      fp16 autocast of cpu/trainer.py:96,203,346-362); "bf16op" = bf16 operands on fp32 tensors (A/B only)
         if impl not in TRAIN_IMPLS:
             raise _lib.TactileSRHipError(f"train_impl {impl!r}: expected one of {sorted(TRAIN_IMPLS)}")
         self.impl = impl
         self.nsplit = TRAIN_IMPLS[impl]
-        self.f16 = self.nsplit == -2
-        self.io16 = self.nsplit == -1
+        self.f16 = self.nsplit == NS_F16X3
+        self.io16 = self.nsplit == NS_B16
         self.act_dtype = torch.bfloat16 if self.io16 else torch.float32
-
-    def _timed(self, key):
-        """Context manager: bracket the launches inside with two HIP events when profiling is on."""
-        eng = self
-
-        class _T:
-            def __enter__(self_):
-                self_.on = eng.profile is not None
-                if self_.on:
-                    self_.e0, self_.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    self_.e0.record()
-
-            def __exit__(self_, *exc):
-                if self_.on:
-                    self_.e1.record()
-                    eng.profile.setdefault(key, []).append((self_.e0, self_.e1))
-                return False
-        return _T()
 
     def _mfma_convs(self):
         m = self.m
@@ -216,18 +199,11 @@ class TrainEngine:
         for i, k in enumerate(cv):
             c.wamax[id(k)] = mx[i:i + 1]
 
-    def _amax_pool(self, c, dev):
-        n = 64 + 8 * (len(self.m.patternFeatureExtra_layer) + len(self.m.forceFeatureExtra_layer) + self.m.seqsCnt)
-        pool = torch.zeros(n, dtype=torch.float32, device=dev) if self.f16 else None
-        state = [0]
+    def _amax_slots(self):
+        return 64 + 8 * (len(self.m.patternFeatureExtra_layer) + len(self.m.forceFeatureExtra_layer) + self.m.seqsCnt)
 
-        def new():
-            if pool is None:
-                return None
-            i = state[0]
-            state[0] += 1
-            return pool[i:i + 1]
-        return new
+    def _amax_pool(self, dev):
+        return _SlotPool(self._amax_slots(), dev, self.f16)
 
     # ------------------------------------------------------------------ helpers
     def _bn_finalize(self, c: _Ctx, conv_bias, bn, slab, cnt, entries, C):
@@ -279,7 +255,7 @@ class TrainEngine:
         return Act(a.mat, a.c, 0, a.c)
 
     def _b16k(self, cout, cin, ks):
-        """bf16 storage: this forward conv shape runs csrc/conv_b16k.hip (tsr_conv2d_ex, nsplit = -3)."""
+        """bf16 storage: this forward conv shape runs csrc/conv_b16k.hip (tsr_conv2d_ex, NS_B16K)."""
         return self.io16 and ks > 1 and bool(_lib.load().tsr_conv2d_ex_dgrad_b16k(cout, cin, ks))
 
     def _packw_b16k(self, conv):
@@ -291,7 +267,7 @@ class TrainEngine:
 
     def _pair_bn(self, c: _Ctx, X: Act, blk, cat1):
         """bf16 storage: conv_3_1 || conv_5_1 of an MSRB (reference model/tactileSR_model.py:198-200) as ONE 5x5 launch with
-        128 output channels on conv_b16k (tsr_conv2d_ex, nsplit = -4: the 3x3 weight sits in the inner taps of its half) and
+        128 output channels on conv_b16k (tsr_conv2d_ex, NS_B16K_PAIR: the 3x3 weight sits in the inner taps of its half) and
         ONE statistics pass over the 128 channels; returns the 4x128 BN vectors [conv_3_1 | conv_5_1]."""
         c3, b3, c5, b5 = blk.conv_3_1[0], blk.conv_3_1[1], blk.conv_5_1[0], blk.conv_5_1[1]
         if b3.momentum != b5.momentum or b3.eps != b5.eps or (c3.bias is None) != (c5.bias is None):
@@ -300,9 +276,9 @@ class TrainEngine:
         w = torch.cat([torch.nn.functional.pad(c3.weight.detach(), (1, 1, 1, 1)), c5.weight.detach()], 0).contiguous()
         wp = torch.empty(_lib.load().tsr_conv_weight_b16k_pair_elems(cin), dtype=torch.bfloat16, device=w.device)
         call("tsr_pack_conv_weight_b16k_pair", ptr(w), ptr(wp), _I(cin), stream())
-        with self._timed(("fwd", 5, 128, cin)):
+        with _timed(self.profile, ("fwd", 5, 128, cin)):
             conv_ex(B=c.B, H=c.H, W=c.W, src=self._plain(c, X), w=wp, cout=128, ks=5, out=cat1, out_ctot=128, out_coff=0,
-                    epi_mode=1, slab=c.slab, slab_cnt=c.slab_cnt, nsplit=-4)
+                    epi_mode=1, slab=c.slab, slab_cnt=c.slab_cnt, nsplit=NS_B16K_PAIR)
         cat = lambda a, b: torch.cat([a.detach(), b.detach()])
         vec = torch.empty(4, 128, dtype=torch.float32, device=w.device)
         rm, rv = cat(b3.running_mean, b5.running_mean), cat(b3.running_var, b5.running_var)
@@ -321,10 +297,10 @@ class TrainEngine:
         w = conv.weight
         cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
         if self._b16k(cout, cin, ks):
-            src, wp, wis, ns = self._plain(c, src), self._packw_b16k(conv), None, -3
+            src, wp, wis, ns = self._plain(c, src), self._packw_b16k(conv), None, NS_B16K
         else:
             (wp, wis), ns = self._packw(c, conv), self.nsplit
-        with self._timed(("fwd", ks, cout, cin)):
+        with _timed(self.profile, ("fwd", ks, cout, cin)):
             conv_ex(B=c.B, H=c.H, W=c.W, src=src, w=wp, cout=cout, ks=ks, out=out, out_ctot=out_ctot,
                     out_coff=out_coff, epi_mode=1, slab=c.slab, slab_cnt=c.slab_cnt, nsplit=ns,
                     w_amax=wis, out_amax=out_amax)
@@ -345,7 +321,7 @@ class TrainEngine:
         e64 = max(lib.tsr_conv2d_slab_entries_ex(B, H, W, 64, k, self.nsplit) for k in (1, 3, 5))
         e128 = max(c.entries, max(lib.tsr_conv2d_slab_entries_ex(B, H, W, 128, k, self.nsplit) for k in (1, 3, 5)))
         if self.io16:
-            e128 = max(e128, lib.tsr_conv2d_slab_entries_ex(B, H, W, 128, 1, -3))
+            e128 = max(e128, lib.tsr_conv2d_slab_entries_ex(B, H, W, 128, 1, NS_B16K))
         c.slab = torch.empty(max(e128 * 128 * 2, e64 * 64 * 2, st_entries * 64 * 2), dtype=torch.float32, device=dev)
         c.slab_cnt = torch.empty(max(e128, e64, st_entries), dtype=torch.float32, device=dev)
         c.work = torch.empty(512 * 128 * 3, dtype=torch.float64, device=dev)
@@ -373,10 +349,10 @@ class TrainEngine:
         s.A1, s.A2 = A1, A2
         if self.io16 and _lib.load().tsr_conv2d_ex_fwd1x1_b16k(64, 256):
             # bf16 storage: the virtual 256-channel input is transformed in LDS behind the DMA (csrc/conv1x1_b16k.hip)
-            wp, wis, nsc = self._packw_b16k(blk.confusion), None, -3
+            wp, wis, nsc = self._packw_b16k(blk.confusion), None, NS_B16K
         else:
             (wp, wis), nsc = self._packw(c, blk.confusion), self.nsplit
-        with self._timed(("fwd", 1, 64, 256)):
+        with _timed(self.profile, ("fwd", 1, 64, 256)):
             conv_ex(B=c.B, H=c.H, W=c.W, src=A2, w=wp, cout=64, ks=1, out=out, out_ctot=octot, out_coff=ocoff,
                     shift=blk.confusion.bias.detach(), relu=1, res=X, nsplit=nsc, w_amax=wis,
                     out_amax=am_o)
@@ -390,12 +366,12 @@ class TrainEngine:
         s.f1 = buf(64)
         s.F1 = Act(s.f1, 64, 0, 64, amax=new_amax())
         if self._b16k(64, 64, 3) and F0.scale is None:       # bf16 storage: both convs on conv_b16k's plain mode
-            (w1, wis1), (w2, wis2), nsr = (self._packw_b16k(rb.conv1), None), (self._packw_b16k(rb.conv2), None), -3
+            (w1, wis1), (w2, wis2), nsr = (self._packw_b16k(rb.conv1), None), (self._packw_b16k(rb.conv2), None), NS_B16K
         else:
             w1, wis1 = self._packw(c, rb.conv1)
             w2, wis2 = self._packw(c, rb.conv2)
             nsr = self.nsplit
-        with self._timed(("fwd", 3, 64, 64)):
+        with _timed(self.profile, ("fwd", 3, 64, 64)):
             conv_ex(B=c.B, H=c.H, W=c.W, src=F0, w=w1, cout=64, ks=3, out=s.f1, out_ctot=64, out_coff=0,
                     shift=rb.conv1.bias.detach(), relu=1, nsplit=nsr, w_amax=wis1, out_amax=s.F1.amax)
             conv_ex(B=c.B, H=c.H, W=c.W, src=s.F1, w=w2, cout=64, ks=3, out=out, out_ctot=octot,
@@ -422,7 +398,7 @@ class TrainEngine:
             return torch.empty(B * ch * HW, dtype=self.act_dtype, device=dev)
 
         self._weight_scales(c)
-        new_amax = self._amax_pool(c, dev)
+        new_amax = self._amax_pool(dev)
         ctot_in = x.shape[1]
         # ---- pattern stems
         c.z1, c.bn1, c.am_z1 = [], [], []
@@ -483,7 +459,7 @@ class TrainEngine:
         # ---- head
         c.h0 = buf(128)
         if self._b16k(128, 128, 3):
-            wh, wish, nsh = self._packw_b16k(m.output_layer[0]), None, -3
+            wh, wish, nsh = self._packw_b16k(m.output_layer[0]), None, NS_B16K
         else:
             (wh, wish), nsh = self._packw(c, m.output_layer[0]), self.nsplit
         conv_ex(B=B, H=H, W=W, src=Act(c.hcat, 128, 0, 128, amax=c.am_hcat), w=wh, cout=128, ks=3, out=c.h0,
@@ -503,7 +479,6 @@ class TrainEngine:
         oracle's ``ReluTap`` (test plumbing: the parity tests evaluate the fp64 gradient on exactly this pattern).
         BN layers store the raw conv output z plus per-channel (scale, shift); every kernel evaluates
         ``fmaf(z, scale, shift) > 0``, whose sign equals that of the exactly evaluated z*scale+shift in fp64."""
-        from .tactileSR_model import from_cb16
         m = self.m
         H, W = c.H, c.W
         B = c.B - img0 if nimg is None else nimg
@@ -562,7 +537,7 @@ class TrainEngine:
         n = cout * cin * ks * ks
         slab = torch.empty(ns * n, dtype=torch.float32, device=w.device)
         bslab = torch.empty(ns * cout, dtype=torch.float32, device=w.device) if with_bias else None
-        with self._timed(("wgrad", ks, cout, cin)):
+        with _timed(self.profile, ("wgrad", ks, cout, cin)):
             if self.nsplit:
                 call("tsr_conv2d_wgrad_bf16s", ptr(a.buf), _I(a.ctot), _I(a.coff), _I(cin), ptr(a.scale), ptr(a.shift),
                      ptr(dz.buf), _I(dz.ctot), _I(dz.coff), _I(cout), _I(ks), _I(self.nsplit), ptr(a.amax),
@@ -585,13 +560,13 @@ class TrainEngine:
         w = conv.weight.detach().contiguous()
         cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
         wa = c.wamax.get(id(conv))
-        # bf16 storage: the 128-channel 3x3 / 5x5 dgrads (masked or not) run conv_b16k (nsplit -3; same tensors, its own pack)
+        # bf16 storage: the 128-channel 3x3 / 5x5 dgrads (masked or not) run conv_b16k (NS_B16K; same tensors, its own pack)
         ns = self.nsplit
         if self.io16 and dz.scale is None and (res is None or res.scale is None) and \
                 (ks > 1 or (mask is not None and res is None)) and _lib.load().tsr_conv2d_ex_dgrad_b16k(nprime, cout, ks):
-            ns = -3
+            ns = NS_B16K
         wp = _pack_dgrad(w, cout, cin, ks, ci0, nprime, ns, wa)
-        with self._timed(("dgrad", ks, nprime, cout)):
+        with _timed(self.profile, ("dgrad", ks, nprime, cout)):
             conv_ex(B=c.B, H=c.H, W=c.W, src=dz, w=wp, cout=nprime, ks=ks, out=out, out_ctot=out_ctot,
                     out_coff=out_coff, res=res, epi_mode=2 if mask is not None else 0, mask=mask, bn=bn,
                     slab=c.slab if bn else None, slab_cnt=None, nsplit=ns, w_amax=wa,
@@ -692,7 +667,7 @@ class TrainEngine:
         def buf(ch):
             return torch.empty(B * ch * HW, dtype=self.act_dtype, device=dev)
 
-        new_amax = self._amax_pool(c, dev)      # a gradient tensor consumed by an MFMA launch carries max|.|
+        new_amax = self._amax_pool(dev)      # a gradient tensor consumed by an MFMA launch carries max|.|
         dout = dout.contiguous().float()
         # taxel gradient (only when the input requires grad): frame 0 gets the force stem's store, then its pattern stem's add
         dx = torch.empty(c.x.shape, dtype=torch.float32, device=dev) if c.want_dx else None
@@ -829,25 +804,15 @@ class BlockEngine(TrainEngine):
             return [b.conv_3_1[0], b.conv_5_1[0], b.conv_3_2[0], b.conv_5_2[0], b.confusion]
         return [b.conv1, b.conv2]
 
-    def _amax_pool(self, c, dev):
-        pool = torch.zeros(64, dtype=torch.float32, device=dev) if self.f16 else None
-        state = [0]
-
-        def new():
-            if pool is None:
-                return None
-            i = state[0]
-            state[0] += 1
-            return pool[i:i + 1]
-        return new
+    def _amax_slots(self):
+        return 64
 
     def forward(self, x: torch.Tensor):
-        from .tactileSR_model import to_cb16, from_cb16
         B, C, H, W = x.shape
         dev = x.device
         c = self._new_ctx(B, H, W, dev)
         self._weight_scales(c)
-        new_amax = self._amax_pool(c, dev)
+        new_amax = self._amax_pool(dev)
 
         def buf(ch):
             return torch.empty(B * ch * H * W, dtype=self.act_dtype, device=dev)
@@ -865,11 +830,10 @@ class BlockEngine(TrainEngine):
 
     def backward(self, c: _Ctx, dout: torch.Tensor):
         from ..ddp import GradSink
-        from .tactileSR_model import to_cb16, from_cb16
         dev = dout.device
         B, H, W = c.B, c.H, c.W
         grads = GradSink(self, dict(self.block.named_parameters()), dev, token=c)
-        new_amax = self._amax_pool(c, dev)
+        new_amax = self._amax_pool(dev)
 
         def buf(ch):
             return torch.empty(B * ch * H * W, dtype=self.act_dtype, device=dev)

@@ -12,7 +12,8 @@ containers only.  There is no CPU fallback: CPU tensors or a missing library rai
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+import math
+from typing import Dict, Optional
 
 import torch
 import torch.nn as nn
@@ -113,50 +114,20 @@ class MSRB(_StandaloneBlock):
         self._standalone_init()
 
     def _build_plan(self):
-        ns = CONV_IMPLS[self.conv_impl]
-        if ns == -2:
-            pair = _PackedPair(self.conv_3_1, self.conv_5_1)
-            halves = tuple(_PackedHalf(self.confusion.weight.detach()[:, o:o + 128], ns) for o in (0, 128))
-            return (pair, None, _PackedConv(self.conv_3_2[0], self.conv_3_2[1], ns, cin_perm=pair.perm),
-                    _PackedConv(self.conv_5_2[0], self.conv_5_2[1], ns, cin_perm=pair.perm),
-                    _PackedConv(self.confusion, None, ns), halves)
-        return (_PackedConv(self.conv_3_1[0], self.conv_3_1[1], ns), _PackedConv(self.conv_5_1[0], self.conv_5_1[1], ns),
-                _PackedConv(self.conv_3_2[0], self.conv_3_2[1], ns), _PackedConv(self.conv_5_2[0], self.conv_5_2[1], ns),
-                _PackedConv(self.confusion, None, ns), None)
+        return _msrb_plan(self, CONV_IMPLS[self.conv_impl], True, True, False)
 
     def _eval_forward(self, x):
         B, _, H, W = x.shape
-        f16 = CONV_IMPLS[self.conv_impl] == -2
-        am = torch.zeros(2, dtype=torch.float32, device=x.device) if f16 else None
-        s_x, s_o = (am[0:1], am[1:2]) if f16 else (None, None)
-        if f16:
+        slot = _SlotPool(4, x.device, CONV_IMPLS[self.conv_impl] == NS_F16X3)
+        s_x, s_o = slot(), slot()
+        if s_x is not None:
             s_x.copy_(x.abs().amax())
-        return from_cb16(self._eval_cb16(to_cb16(x), B, H, W, s_x, s_o), B, 64, H, W)
-
-    def _eval_cb16(self, xa, B, H, W, s_x, s_o):
-        """The block on a CB16 fp32 buffer (B, 64, H, W) -> a new CB16 buffer; ``s_x`` / ``s_o``: the device scalars
-        holding max|input| / receiving max|output| (fp16x3 operand scales; None for the other arithmetic modes)."""
-        c31, c51, c32, c52, conf, halves = self._get_plan()
-        dev = xa.device
-        f16 = CONV_IMPLS[self.conv_impl] == -2
-        am = torch.zeros(2, dtype=torch.float32, device=dev) if f16 else None
-        s_c1, s_c2 = (am[0:1], am[1:2]) if f16 else (None, None)
-        cat1 = torch.empty(B * 128 * H * W, dtype=torch.float32, device=dev)
-        out = torch.empty(B * 64 * H * W, dtype=torch.float32, device=dev)
-        if halves is not None:
-            p1 = torch.empty_like(out)
-            TactileSR._conv_pair(self, c31, xa, cat1, B, H, W, s_x, s_c1)
-            TactileSR._conv_fused(self, c32, halves[0], conf.shift, cat1, p1, 64, 0, xa, 64, 0, False, None, s_c1, B, H, W)
-            TactileSR._conv_fused(self, c52, halves[1], None, cat1, out, 64, 0, p1, 64, 0, True, s_o, s_c1, B, H, W)
-        else:
-            cat2 = torch.empty(B * 256 * H * W, dtype=torch.float32, device=dev)
-            TactileSR._conv(self, c31, xa, 64, 0, cat1, 128, 0, True, B, H, W, amax_in=s_x, amax_out=s_c1)
-            TactileSR._conv(self, c51, xa, 64, 0, cat1, 128, 64, True, B, H, W, amax_in=s_x, amax_out=s_c1)
-            TactileSR._conv(self, c32, cat1, 128, 0, cat2, 256, 0, True, B, H, W, amax_in=s_c1, amax_out=s_c2)
-            TactileSR._conv(self, c52, cat1, 128, 0, cat2, 256, 128, True, B, H, W, amax_in=s_c1, amax_out=s_c2)
-            TactileSR._conv(self, conf, cat2, 256, 0, out, 64, 0, True, B, H, W, res=xa, r_ctot=64, r_coff=0,
-                            amax_in=s_c2, amax_out=s_o)
-        return out
+        xa = to_cb16(x)
+        out = torch.empty_like(xa)
+        plan = self._get_plan()
+        ws = _msrb_workspace(plan.halves is not None, xa, B * H * W)
+        _run_msrb(plan, self._profile, xa, s_x, out, 64, 0, s_o, ws, slot, B, H, W)
+        return from_cb16(out, B, 64, H, W)
 
 
 class ResBlock(_StandaloneBlock):
@@ -170,33 +141,74 @@ class ResBlock(_StandaloneBlock):
         self._standalone_init()
 
     def _build_plan(self):
-        ns = CONV_IMPLS[self.conv_impl]
-        return _PackedConv(self.conv1, None, ns), _PackedConv(self.conv2, None, ns)
+        return _res_plan(self, CONV_IMPLS[self.conv_impl])
 
     def _eval_forward(self, x):
-        c1, c2 = self._get_plan()
         B, _, H, W = x.shape
-        dev = x.device
-        f16 = CONV_IMPLS[self.conv_impl] == -2
-        am = torch.zeros(3, dtype=torch.float32, device=dev) if f16 else None
-        s_x, s_1, s_o = (am[i:i + 1] for i in range(3)) if f16 else (None,) * 3
-        if f16:
+        slot = _SlotPool(3, x.device, CONV_IMPLS[self.conv_impl] == NS_F16X3)
+        s_x, s_o = slot(), slot()
+        if s_x is not None:
             s_x.copy_(x.abs().amax())
         xa = to_cb16(x)
         f1, out = torch.empty_like(xa), torch.empty_like(xa)
-        TactileSR._conv(self, c1, xa, 64, 0, f1, 64, 0, True, B, H, W, amax_in=s_x, amax_out=s_1)
-        TactileSR._conv(self, c2, f1, 64, 0, out, 64, 0, True, B, H, W, res=xa, r_ctot=64, r_coff=0, amax_in=s_1,
-                        amax_out=s_o)
+        _run_res(self._get_plan(), self._profile, xa, s_x, out, 64, 0, s_o, f1, slot, B, H, W)
         return from_cb16(out, B, 64, H, W)
 
 
-CONV_IMPLS = {"f32": 0, "bf16x6": 3, "bf16x3": 2, "bf16": 1, "fp16x3": -2}   # name -> split planes (0 = fp32 MFMA,
-#                                                                              negative = fp16 planes with scaling)
+# Arithmetic codes of the C ABI (`nsplit` of include/tactilesr_hip.h): 1..3 = that many bf16 planes, and
+NS_F32 = 0          # fp32 MFMA
+NS_F16X3 = -2       # two power-of-two-scaled fp16 planes, three products
+NS_B16 = -1         # train: bf16 activation / gradient storage
+NS_B16K = -3        # train: the bf16-storage forms that run on conv_b16k / conv1x1_b16k
+NS_B16K_PAIR = -4   # train: the bf16-storage stage-1 pair (one 5x5 launch on conv_b16k)
+CONV_IMPLS = {"f32": NS_F32, "bf16x6": 3, "bf16x3": 2, "bf16": 1, "fp16x3": NS_F16X3}   # eval: one plane = bf16 storage
+
+
+def _pow2_wscale(max_abs: float) -> float:
+    """fp16 planes: the power-of-two weight scale that puts max|w| * wscale in [2^13, 2^14)."""
+    return 2.0 ** (13 - math.floor(math.log2(max_abs))) if max_abs > 0 else 1.0
+
+
+class _SlotPool:
+    """fp16x3: one device scalar per logical activation tensor holds max|x| (atomic max by the producer's epilogue; the
+    consumer derives its power-of-two input scale from it).  `pool()` hands out the next 1-element view of ONE zeroed
+    buffer; a pool that is not `enabled` (every other arithmetic) hands out None."""
+    __slots__ = ("buf", "used")
+
+    def __init__(self, n, device, enabled):
+        self.buf = torch.zeros(n, dtype=torch.float32, device=device) if enabled else None
+        self.used = 0
+
+    def __call__(self):
+        if self.buf is None:
+            return None
+        self.used += 1
+        return self.buf[self.used - 1:self.used]
+
+
+class _timed:
+    """`with _timed(prof, key):` brackets the launches inside with two HIP events on the launch stream and appends the
+    pair to `prof[key]` (bench.py); with `prof` None it does nothing and creates no event."""
+    __slots__ = ("prof", "key", "ev")
+
+    def __init__(self, prof, key):
+        self.prof, self.key = prof, key
+
+    def __enter__(self):
+        if self.prof is not None:
+            self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            self.ev[0].record()
+
+    def __exit__(self, *exc):
+        if self.prof is not None:
+            self.ev[1].record()
+            self.prof.setdefault(self.key, []).append(self.ev)
+        return False
 
 
 class _PackedConv:
     """Device-side constants of one conv launch: packed weight, folded scale/shift."""
-    __slots__ = ("w", "scale", "shift", "cin", "cout", "ks", "nsplit", "w_inv_scale", "b16k")
+    __slots__ = ("w", "scale", "shift", "cin", "cout", "ks", "nsplit", "w_inv_scale", "io16", "b16k")
 
     def __init__(self, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d], nsplit: int = 0, cin_perm=None):
         w = conv.weight.detach().float()
@@ -206,25 +218,23 @@ class _PackedConv:
         self.cout, self.cin, self.ks = w.shape[0], w.shape[1], w.shape[2]
         self.nsplit = nsplit
         self.w_inv_scale = 1.0
-        # bf16 activation storage (nsplit 1 is only ever that path's): the 3x3 / 5x5 convs run csrc/conv_b16k.hip
+        self.io16 = nsplit == CONV_IMPLS["bf16"]
+        # bf16 activation storage (one plane is only ever that path's): the 3x3 / 5x5 convs run csrc/conv_b16k.hip
         # (its 64-channel instantiations -- 16 MFMAs per barrier step -- measure slower than the 32x32x16 kernel's 3-tap steps:
         #  3x3 64->64 0.83 vs 0.70 ms per launch at B = 4096; they stay on that kernel)
-        self.b16k = nsplit == 1 and self.ks > 1 and self.cin % 32 == 0 and self.cout == 128
+        self.b16k = self.io16 and self.ks > 1 and self.cin % 32 == 0 and self.cout == 128
         if self.b16k:
             n = _lib.load().tsr_conv_weight_b16k_elems(self.cout, self.cin, self.ks)
             self.w = torch.empty(n, dtype=torch.bfloat16, device=w.device)
             call("tsr_pack_conv_weight_b16k", ptr(w), ptr(self.w), _I(self.cout), _I(self.cin), _I(self.ks), stream())
-        elif nsplit == -2:
-            # fp16 planes: power-of-two weight scale so that max|w|*wscale lies in [2^13, 2^14)
-            import math
-            m = float(w.abs().max())
-            wscale = 2.0 ** (13 - math.floor(math.log2(m))) if m > 0 else 1.0
+        elif nsplit == NS_F16X3:
+            wscale = _pow2_wscale(float(w.abs().max()))
             self.w_inv_scale = 1.0 / wscale
             n = _lib.load().tsr_conv_weight_bf16s_elems(self.cout, self.cin, self.ks, 2)
             self.w = torch.empty(n, dtype=torch.float16, device=w.device)
             call("tsr_pack_conv_weight_f16s", ptr(w), ptr(self.w), _I(self.cout), _I(self.cin), _I(self.ks),
                  _lib.c_float(wscale), stream())
-        elif nsplit == 0:
+        elif nsplit == NS_F32:
             self.w = torch.empty_like(w)
             call("tsr_pack_conv_weight", ptr(w), ptr(self.w), _I(self.cout), _I(self.cin), _I(self.ks), stream())
         else:
@@ -240,6 +250,7 @@ class _PackedPair:
     stream, folded BN scale / shift in the kernel's channel order, and that order (`perm[k]` = channel of
     cat([conv3, conv5]) held by kernel channel k) for the consumers' weights."""
     __slots__ = ("w", "scale", "shift", "cin", "w_inv_scale", "perm")
+    b16k = False
     _perm = None
 
     @classmethod
@@ -252,12 +263,10 @@ class _PackedPair:
         return torch.tensor(cls._perm, dtype=torch.long, device=device)
 
     def __init__(self, seq3: nn.Sequential, seq5: nn.Sequential):
-        import math
         w3 = seq3[0].weight.detach().float().contiguous()
         w5 = seq5[0].weight.detach().float().contiguous()
         self.cin = w3.shape[1]
-        m = max(float(w3.abs().max()), float(w5.abs().max()))
-        wscale = 2.0 ** (13 - math.floor(math.log2(m))) if m > 0 else 1.0
+        wscale = _pow2_wscale(max(float(w3.abs().max()), float(w5.abs().max())))
         self.w_inv_scale = 1.0 / wscale
         self.w = torch.empty(_lib.load().tsr_conv_weight_pair_elems(self.cin), dtype=torch.float16, device=w3.device)
         call("tsr_pack_conv_weight_pair_f16s", ptr(w3), ptr(w5), ptr(self.w), _I(self.cin), _lib.c_float(wscale),
@@ -274,6 +283,8 @@ class _PackedPairB16:
     conv_3_1 (its 3x3 weight zero-padded to 5x5; the kernel skips those taps) and whose last 64 are conv_5_1 -- packed by
     the ordinary one-plane pack -- with the two folded BatchNorm vectors concatenated.  `cat1` comes out in torch.cat order."""
     __slots__ = ("w", "scale", "shift", "cin")
+    b16k = True
+    perm = None          # `cat1` in torch.cat order: nothing to permute downstream
 
     def __init__(self, seq3: nn.Sequential, seq5: nn.Sequential):
         w3 = seq3[0].weight.detach().float()
@@ -293,16 +304,14 @@ class _PackedHalf:
     """One 64x128x1x1 half of an MSRB's `confusion` weight in the fp16 two-plane pack (fused 1x1 epilogue)."""
     __slots__ = ("w", "w_inv_scale")
 
-    def __init__(self, w: torch.Tensor, ns: int = -2):
-        import math
+    def __init__(self, w: torch.Tensor, ns: int):
         w = w.float().contiguous()
-        if ns != -2:        # bf16-storage path: one bf16 plane, no scaling
+        if ns != NS_F16X3:        # bf16-storage path: one bf16 plane, no scaling
             self.w_inv_scale = 1.0
             self.w = torch.empty(64 * 128, dtype=torch.bfloat16, device=w.device)
             call("tsr_pack_w2_b16k", ptr(w), ptr(self.w), stream())
             return
-        m = float(w.abs().max())
-        wscale = 2.0 ** (13 - math.floor(math.log2(m))) if m > 0 else 1.0
+        wscale = _pow2_wscale(float(w.abs().max()))
         self.w_inv_scale = 1.0 / wscale
         n = _lib.load().tsr_conv_weight_bf16s_elems(64, 128, 1, 2)
         self.w = torch.empty(n, dtype=torch.float16, device=w.device)
@@ -320,6 +329,129 @@ def _fold(bias, bn: Optional[nn.BatchNorm2d], cout: int, device):
     b = bias.detach().float() if bias is not None else torch.zeros(cout, device=device)
     shift = (b - bn.running_mean.detach().float()) * scale + bn.bias.detach().float()
     return scale.contiguous(), shift.contiguous()
+
+
+class _MSRBPlan:
+    """Packed constants of one MSRB.  Stage 1 is either `pair` (one launch; `c31` / `c51` None) or the two convs `c31` /
+    `c51` (`pair` None); `halves` = the two 64x128 halves of the 1x1 `confusion` for the fused stage 2, or None (stage 2
+    writes `cat2` and `conf` runs as a launch of its own; fused, only `conf.shift` is read)."""
+    __slots__ = ("pair", "c31", "c51", "c32", "c52", "conf", "halves")
+
+
+class _ResPlan:
+    __slots__ = ("c1", "c2")
+
+
+def _msrb_plan(blk, ns, fuse_pair, fuse_1x1, bf16_storage) -> _MSRBPlan:
+    """Pack one MSRB for arithmetic `ns`.  `fuse_pair` / `fuse_1x1` take effect where the kernels exist: fp16x3 and the
+    bf16-storage path."""
+    p = _MSRBPlan()
+    has_fused = ns == NS_F16X3 or bf16_storage
+    p.halves = p.pair = p.c31 = p.c51 = None
+    if fuse_1x1 and has_fused:
+        p.halves = tuple(_PackedHalf(blk.confusion.weight.detach()[:, o:o + 128], ns) for o in (0, 128))
+    if fuse_pair and has_fused:
+        # stage 1 as ONE launch (3x3 || 5x5 on one staged halo); the fp16x3 kernel leaves cat1 in its own channel order
+        # and the stage-2 weights are permuted along C_in to match
+        p.pair = (_PackedPairB16 if bf16_storage else _PackedPair)(blk.conv_3_1, blk.conv_5_1)
+    else:
+        p.c31 = _PackedConv(blk.conv_3_1[0], blk.conv_3_1[1], ns)
+        p.c51 = _PackedConv(blk.conv_5_1[0], blk.conv_5_1[1], ns)
+    perm = p.pair.perm if p.pair is not None else None
+    p.c32 = _PackedConv(blk.conv_3_2[0], blk.conv_3_2[1], ns, cin_perm=perm)
+    p.c52 = _PackedConv(blk.conv_5_2[0], blk.conv_5_2[1], ns, cin_perm=perm)
+    p.conf = _PackedConv(blk.confusion, None, ns)
+    return p
+
+
+def _res_plan(rb, ns) -> _ResPlan:
+    p = _ResPlan()
+    p.c1, p.c2 = _PackedConv(rb.conv1, None, ns), _PackedConv(rb.conv2, None, ns)
+    return p
+
+
+def _conv(prof, pc: _PackedConv, src, s_ctot, s_coff, dst, d_ctot, d_coff, relu, B, H, W, res=None, r_ctot=0, r_coff=0,
+          amax_in=None, amax_out=None):
+    with _timed(prof, (pc.ks, pc.cout)):     # bench.py: per kernel instantiation
+        if pc.io16:      # bf16 activation storage
+            call("tsr_conv2d_fwd_b16k" if pc.b16k else "tsr_conv2d_fwd_b16", ptr(src), _I(s_ctot), _I(s_coff), _I(pc.cin),
+                 ptr(pc.w), _I(pc.cout), _I(pc.ks), ptr(pc.scale), ptr(pc.shift), ptr(res), _I(r_ctot), _I(r_coff),
+                 ptr(dst), _I(d_ctot), _I(d_coff), _I(1 if relu else 0), _I(B), _I(H), _I(W), stream())
+        elif pc.nsplit == NS_F16X3:
+            call("tsr_conv2d_fwd_f16s", ptr(src), _I(s_ctot), _I(s_coff), _I(pc.cin), ptr(pc.w), _I(pc.cout),
+                 _I(pc.ks), _lib.c_float(pc.w_inv_scale), ptr(amax_in), ptr(amax_out), ptr(pc.scale), ptr(pc.shift),
+                 ptr(res), _I(r_ctot), _I(r_coff), ptr(dst), _I(d_ctot), _I(d_coff), _I(1 if relu else 0),
+                 _I(B), _I(H), _I(W), stream())
+        elif pc.nsplit == NS_F32:
+            call("tsr_conv2d_fwd", ptr(src), _I(s_ctot), _I(s_coff), _I(pc.cin), ptr(pc.w), _I(pc.cout), _I(pc.ks),
+                 ptr(pc.scale), ptr(pc.shift), ptr(res), _I(r_ctot), _I(r_coff),
+                 ptr(dst), _I(d_ctot), _I(d_coff), _I(1 if relu else 0), _I(B), _I(H), _I(W), stream())
+        else:
+            call("tsr_conv2d_fwd_bf16s", ptr(src), _I(s_ctot), _I(s_coff), _I(pc.cin), ptr(pc.w), _I(pc.cout),
+                 _I(pc.ks), _I(pc.nsplit), ptr(pc.scale), ptr(pc.shift), ptr(res), _I(r_ctot), _I(r_coff),
+                 ptr(dst), _I(d_ctot), _I(d_coff), _I(1 if relu else 0), _I(B), _I(H), _I(W), stream())
+
+
+def _conv_pair(prof, pp, src, dst, B, H, W, amax_in, amax_out):
+    """conv_3_1 || conv_5_1 (+ BN + ReLU each) of an MSRB: 64 -> 128 channels of `cat1`, one launch."""
+    with _timed(prof, ("pair", 128)):
+        if pp.b16k:
+            call("tsr_conv2d_fwd_b16k_pair", ptr(src), _I(64), _I(0), _I(pp.cin), ptr(pp.w), ptr(pp.scale), ptr(pp.shift),
+                 ptr(dst), _I(128), _I(0), _I(1), _I(B), _I(H), _I(W), stream())
+        else:
+            call("tsr_conv2d_fwd_f16s_pair", ptr(src), _I(64), _I(0), _I(pp.cin), ptr(pp.w), _lib.c_float(pp.w_inv_scale),
+                 ptr(amax_in), ptr(amax_out), ptr(pp.scale), ptr(pp.shift), ptr(dst), _I(128), _I(0), _I(1),
+                 _I(B), _I(H), _I(W), stream())
+
+
+def _conv_fused(prof, pc: _PackedConv, half: _PackedHalf, shift2, src, dst, d_ctot, d_coff, res, r_ctot, r_coff, relu2,
+                amax_out, amax_in, B, H, W):
+    """Stage-2 conv (128 -> 128, BN + ReLU) + its half of the 1x1 confusion + residual (+ ReLU), one launch."""
+    with _timed(prof, (pc.ks, pc.cout)):
+        if pc.io16:
+            call("tsr_conv2d_fwd_b16k_fuse1x1", ptr(src), _I(128), _I(0), _I(128), ptr(pc.w), _I(pc.ks), ptr(pc.scale),
+                 ptr(pc.shift), _I(1), ptr(half.w), ptr(shift2), ptr(res), _I(r_ctot), _I(r_coff), ptr(dst), _I(d_ctot),
+                 _I(d_coff), _I(1 if relu2 else 0), _I(B), _I(H), _I(W), stream())
+        else:
+            call("tsr_conv2d_fwd_f16s_fuse1x1", ptr(src), _I(128), _I(0), _I(128), ptr(pc.w), _I(pc.ks),
+                 _lib.c_float(pc.w_inv_scale), ptr(amax_in), ptr(amax_out), ptr(pc.scale), ptr(pc.shift), _I(1),
+                 ptr(half.w), _lib.c_float(half.w_inv_scale), ptr(shift2), ptr(res), _I(r_ctot), _I(r_coff),
+                 ptr(dst), _I(d_ctot), _I(d_coff), _I(1 if relu2 else 0), _I(B), _I(H), _I(W), stream())
+
+
+def _msrb_workspace(fused: bool, like: torch.Tensor, BHW: int):
+    """Scratch of `_run_msrb`, reusable from block to block: `cat1` (128 channels) and, with the 1x1 fused, the partial
+    sum `p1` (64) -- else `cat2` (256)."""
+    return like.new_empty(128 * BHW), like.new_empty((64 if fused else 256) * BHW)
+
+
+def _run_msrb(p: _MSRBPlan, prof, src, s_in, dst, d_ctot, d_coff, s_out, ws, slot, B, H, W):
+    """The eval launches of one MSRB: the 64-channel CB16 buffer `src` -> channels [d_coff, d_coff + 64) of `dst`.
+    `s_in` / `s_out`: the max|.| slots of the input / output tensor, `slot`: the pool the block's own two come from."""
+    cat1, ws2 = ws
+    s_c1, s_c2 = slot(), slot()
+    if p.pair is not None:
+        _conv_pair(prof, p.pair, src, cat1, B, H, W, s_in, s_c1)
+    else:
+        _conv(prof, p.c31, src, 64, 0, cat1, 128, 0, True, B, H, W, amax_in=s_in, amax_out=s_c1)
+        _conv(prof, p.c51, src, 64, 0, cat1, 128, 64, True, B, H, W, amax_in=s_in, amax_out=s_c1)
+    if p.halves is not None:
+        # stage 2 with the 1x1 fused: P = W_a.relu(bn(conv3)) + b + x ; out = relu(W_b.relu(bn(conv5)) + P)
+        _conv_fused(prof, p.c32, p.halves[0], p.conf.shift, cat1, ws2, 64, 0, src, 64, 0, False, None, s_c1, B, H, W)
+        _conv_fused(prof, p.c52, p.halves[1], None, cat1, dst, d_ctot, d_coff, ws2, 64, 0, True, s_out, s_c1, B, H, W)
+    else:
+        _conv(prof, p.c32, cat1, 128, 0, ws2, 256, 0, True, B, H, W, amax_in=s_c1, amax_out=s_c2)
+        _conv(prof, p.c52, cat1, 128, 0, ws2, 256, 128, True, B, H, W, amax_in=s_c1, amax_out=s_c2)
+        _conv(prof, p.conf, ws2, 256, 0, dst, d_ctot, d_coff, True, B, H, W, res=src, r_ctot=64, r_coff=0,
+              amax_in=s_c2, amax_out=s_out)
+
+
+def _run_res(p: _ResPlan, prof, src, s_in, dst, d_ctot, d_coff, s_out, f1, slot, B, H, W):
+    """The eval launches of one ResBlock: `src` (64 channels) -> channels [d_coff, d_coff + 64) of `dst`; `f1`: scratch."""
+    s_1 = slot()
+    _conv(prof, p.c1, src, 64, 0, f1, 64, 0, True, B, H, W, amax_in=s_in, amax_out=s_1)
+    _conv(prof, p.c2, f1, 64, 0, dst, d_ctot, d_coff, True, B, H, W, res=src, r_ctot=64, r_coff=0, amax_in=s_1,
+          amax_out=s_out)
 
 
 class TactileSR(nn.Module):
@@ -415,33 +547,10 @@ class TactileSR(nn.Module):
             stems.append((seq[1].weight.detach().float().contiguous(), s1, sh1, _PackedConv(seq[4], seq[5], ns)))
         plan["stems"] = stems
         plan["fuse"] = _PackedConv(self.inputContact_layer[0], self.inputContact_layer[1], ns)
-        msrbs = []
-        for blk in self.patternFeatureExtra_layer:
-            halves = None
-            if self.fuse_1x1 and (ns == -2 or self.conv_impl == "bf16"):
-                # the two 64x128 halves of the 1x1, each packed like a 1x1 conv weight
-                halves = tuple(_PackedHalf(blk.confusion.weight.detach()[:, o:o + 128], ns) for o in (0, 128))
-            if self.fuse_pair and ns == -2:
-                # stage 1 as ONE launch (3x3 || 5x5 on one staged halo); cat1 then holds the kernel's channel order and
-                # the stage-2 weights are permuted along C_in to match
-                pair = _PackedPair(blk.conv_3_1, blk.conv_5_1)
-                msrbs.append((pair, None,
-                              _PackedConv(blk.conv_3_2[0], blk.conv_3_2[1], ns, cin_perm=pair.perm),
-                              _PackedConv(blk.conv_5_2[0], blk.conv_5_2[1], ns, cin_perm=pair.perm),
-                              _PackedConv(blk.confusion, None, ns), halves))
-                continue
-            if self.fuse_pair and self.conv_impl == "bf16":
-                # bf16 storage: the same one-launch stage 1 (natural channel order: nothing to permute downstream)
-                msrbs.append((_PackedPairB16(blk.conv_3_1, blk.conv_5_1), None,
-                              _PackedConv(blk.conv_3_2[0], blk.conv_3_2[1], ns), _PackedConv(blk.conv_5_2[0], blk.conv_5_2[1], ns),
-                              _PackedConv(blk.confusion, None, ns), halves))
-                continue
-            msrbs.append((_PackedConv(blk.conv_3_1[0], blk.conv_3_1[1], ns), _PackedConv(blk.conv_5_1[0], blk.conv_5_1[1], ns),
-                          _PackedConv(blk.conv_3_2[0], blk.conv_3_2[1], ns), _PackedConv(blk.conv_5_2[0], blk.conv_5_2[1], ns),
-                          _PackedConv(blk.confusion, None, ns), halves))
-        plan["msrb"] = msrbs
+        plan["msrb"] = [_msrb_plan(blk, ns, self.fuse_pair, self.fuse_1x1, self.conv_impl == "bf16")
+                        for blk in self.patternFeatureExtra_layer]
         plan["force_w"] = self.input_layer_force[1].weight.detach().float().contiguous()
-        plan["res"] = [(_PackedConv(b.conv1, None, ns), _PackedConv(b.conv2, None, ns)) for b in self.forceFeatureExtra_layer]
+        plan["res"] = [_res_plan(rb, ns) for rb in self.forceFeatureExtra_layer]
         plan["head0"] = _PackedConv(self.output_layer[0], None, CONV_IMPLS[self.head_impl] if self.head_impl else ns)
         plan["head_w"] = self.output_layer[2].weight.detach().float().contiguous()
         return plan
@@ -452,70 +561,6 @@ class TactileSR(nn.Module):
             self._plan = self._build_plan()
             self._plan_key = key
         return self._plan
-
-    def _conv(self, pc: _PackedConv, src, s_ctot, s_coff, dst, d_ctot, d_coff, relu, B, H, W, res=None, r_ctot=0,
-              r_coff=0, amax_in=None, amax_out=None):
-        prof = self._profile
-        if prof is not None:     # bench.py: HIP-event bracket on the launch stream, per kernel instantiation
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if pc.nsplit == 1 and src.dtype == torch.bfloat16:      # bf16 activation storage
-            call("tsr_conv2d_fwd_b16k" if pc.b16k else "tsr_conv2d_fwd_b16", ptr(src), _I(s_ctot), _I(s_coff), _I(pc.cin), ptr(pc.w), _I(pc.cout), _I(pc.ks),
-                 ptr(pc.scale), ptr(pc.shift), ptr(res), _I(r_ctot), _I(r_coff), ptr(dst), _I(d_ctot), _I(d_coff),
-                 _I(1 if relu else 0), _I(B), _I(H), _I(W), stream())
-        elif pc.nsplit == -2:
-            call("tsr_conv2d_fwd_f16s", ptr(src), _I(s_ctot), _I(s_coff), _I(pc.cin), ptr(pc.w), _I(pc.cout),
-                 _I(pc.ks), _lib.c_float(pc.w_inv_scale), ptr(amax_in), ptr(amax_out), ptr(pc.scale), ptr(pc.shift),
-                 ptr(res), _I(r_ctot), _I(r_coff), ptr(dst), _I(d_ctot), _I(d_coff), _I(1 if relu else 0),
-                 _I(B), _I(H), _I(W), stream())
-        elif pc.nsplit == 0:
-            call("tsr_conv2d_fwd", ptr(src), _I(s_ctot), _I(s_coff), _I(pc.cin), ptr(pc.w), _I(pc.cout), _I(pc.ks),
-                 ptr(pc.scale), ptr(pc.shift), ptr(res), _I(r_ctot), _I(r_coff),
-                 ptr(dst), _I(d_ctot), _I(d_coff), _I(1 if relu else 0), _I(B), _I(H), _I(W), stream())
-        else:
-            call("tsr_conv2d_fwd_bf16s", ptr(src), _I(s_ctot), _I(s_coff), _I(pc.cin), ptr(pc.w), _I(pc.cout),
-                 _I(pc.ks), _I(pc.nsplit), ptr(pc.scale), ptr(pc.shift), ptr(res), _I(r_ctot), _I(r_coff),
-                 ptr(dst), _I(d_ctot), _I(d_coff), _I(1 if relu else 0), _I(B), _I(H), _I(W), stream())
-        if prof is not None:
-            e1.record()
-            prof.setdefault((pc.ks, pc.cout), []).append((e0, e1))
-
-    def _conv_pair(self, pp: "_PackedPair", src, dst, B, H, W, amax_in, amax_out):
-        """conv_3_1 || conv_5_1 (+ BN + ReLU each) of an MSRB: 64 -> 128 channels of `cat1`, one launch."""
-        prof = self._profile
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if isinstance(pp, _PackedPairB16):
-            call("tsr_conv2d_fwd_b16k_pair", ptr(src), _I(64), _I(0), _I(pp.cin), ptr(pp.w), ptr(pp.scale), ptr(pp.shift),
-                 ptr(dst), _I(128), _I(0), _I(1), _I(B), _I(H), _I(W), stream())
-        else:
-            call("tsr_conv2d_fwd_f16s_pair", ptr(src), _I(64), _I(0), _I(pp.cin), ptr(pp.w), _lib.c_float(pp.w_inv_scale),
-                 ptr(amax_in), ptr(amax_out), ptr(pp.scale), ptr(pp.shift), ptr(dst), _I(128), _I(0), _I(1),
-                 _I(B), _I(H), _I(W), stream())
-        if prof is not None:
-            e1.record()
-            prof.setdefault(("pair", 128), []).append((e0, e1))
-
-    def _conv_fused(self, pc: _PackedConv, half: "_PackedHalf", shift2, src, dst, d_ctot, d_coff, res, r_ctot, r_coff,
-                    relu2, amax_out, amax_in, B, H, W):
-        """Stage-2 conv (128 -> 128, BN + ReLU) + its half of the 1x1 confusion + residual (+ ReLU), one launch."""
-        prof = self._profile
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if src.dtype == torch.bfloat16:
-            call("tsr_conv2d_fwd_b16k_fuse1x1", ptr(src), _I(128), _I(0), _I(128), ptr(pc.w), _I(pc.ks), ptr(pc.scale),
-                 ptr(pc.shift), _I(1), ptr(half.w), ptr(shift2), ptr(res), _I(r_ctot), _I(r_coff), ptr(dst), _I(d_ctot),
-                 _I(d_coff), _I(1 if relu2 else 0), _I(B), _I(H), _I(W), stream())
-        else:
-            call("tsr_conv2d_fwd_f16s_fuse1x1", ptr(src), _I(128), _I(0), _I(128), ptr(pc.w), _I(pc.ks),
-                 _lib.c_float(pc.w_inv_scale), ptr(amax_in), ptr(amax_out), ptr(pc.scale), ptr(pc.shift), _I(1),
-                 ptr(half.w), _lib.c_float(half.w_inv_scale), ptr(shift2), ptr(res), _I(r_ctot), _I(r_coff),
-                 ptr(dst), _I(d_ctot), _I(d_coff), _I(1 if relu2 else 0), _I(B), _I(H), _I(W), stream())
-        if prof is not None:
-            e1.record()
-            prof.setdefault((pc.ks, pc.cout), []).append((e0, e1))
 
     def _infer_pass(self, x: torch.Tensor, out: torch.Tensor, stages=None) -> None:
         """Eval-mode forward of one batch slice; mirrors reference forward :67-84."""
@@ -542,29 +587,18 @@ class TactileSR(nn.Module):
                      ptr(sh1), ptr(dst), _I(64), _I(0), _I(1), _I(B), ptr(slot_), stream())
 
         ctot = x.shape[1]
-        # fp16-split path: one device scalar per logical activation tensor holds max|x| (atomic max by the
-        # producer's epilogue); the consumer derives its power-of-two input scale from it
-        f16 = CONV_IMPLS[self.conv_impl] == -2
-        amax = torch.zeros(16 + 8 * len(plan["msrb"]) + 4 * len(plan["res"]) + T, dtype=torch.float32,
-                           device=dev) if f16 else None
-        nslot = [0]
-
-        def slot():
-            if amax is None:
-                return None
-            i = nslot[0]
-            nslot[0] += 1
-            return amax[i:i + 1]
-
+        prof = self._profile
+        slot = _SlotPool(16 + 8 * len(plan["msrb"]) + 4 * len(plan["res"]) + T, dev,
+                         CONV_IMPLS[self.conv_impl] == NS_F16X3)
         stemA, catT = buf(64), buf(64 * T)
         s_catT = slot()
         for t, (w1, s1, sh1, pc2) in enumerate(plan["stems"]):
             s_stem = slot()
             stem(A * t, w1, s1, sh1, stemA, s_stem)
-            self._conv(pc2, stemA, 64, 0, catT, 64 * T, 64 * t, True, B, H, W, amax_in=s_stem, amax_out=s_catT)
+            _conv(prof, pc2, stemA, 64, 0, catT, 64 * T, 64 * t, True, B, H, W, amax_in=s_stem, amax_out=s_catT)
         xa, xb = buf(64), buf(64)
         s_x = slot()
-        self._conv(plan["fuse"], catT, 64 * T, 0, xa, 64, 0, True, B, H, W, amax_in=s_catT, amax_out=s_x)
+        _conv(prof, plan["fuse"], catT, 64 * T, 0, xa, 64, 0, True, B, H, W, amax_in=s_catT, amax_out=s_x)
         if stages is not None:
             stages["stems"] = (catT, 64 * T)
             stages["fuse"] = (xa.clone(), 64)
@@ -572,52 +606,21 @@ class TactileSR(nn.Module):
         hcat = buf(128)
         s_hcat = slot()
         n_msrb = len(plan["msrb"])
-        fused = n_msrb > 0 and plan["msrb"][0][5] is not None
-        cat1, cat2 = buf(128), (None if fused else buf(256))
-        cur = xa
+        ws = _msrb_workspace(n_msrb > 0 and plan["msrb"][0].halves is not None, xa, B * HW)
         if n_msrb == 0:
             call("tsr_cb16_to_nchw", ptr(xa), ptr(xb), _I(B), _I(64), _I(HW), _I(64), _I(0), stream())
             call("tsr_nchw_to_cb16", ptr(xb), ptr(hcat), _I(B), _I(64), _I(HW), _I(128), _I(64), stream())
-        p1 = None
-        for i, (c31, c51, c32, c52, conf, halves) in enumerate(plan["msrb"]):
-            last = i == n_msrb - 1
-            s_c1, s_c2 = slot(), slot()
-            if c51 is None:      # stage-1 pair kernel
-                self._conv_pair(c31, cur, cat1, B, H, W, s_x, s_c1)
+        cur, nxt = xa, xb
+        for i, p in enumerate(plan["msrb"]):
+            if i == n_msrb - 1:   # pattern feature lands in channels [64,128) of the head input (cat: force first)
+                dst, s_out = (hcat, 128, 64), s_hcat
             else:
-                self._conv(c31, cur, 64, 0, cat1, 128, 0, True, B, H, W, amax_in=s_x, amax_out=s_c1)
-                self._conv(c51, cur, 64, 0, cat1, 128, 64, True, B, H, W, amax_in=s_x, amax_out=s_c1)
-            nxt = xb if cur is xa else xa
-            if halves is not None:
-                # stage 2 with the 1x1 fused: P = W_a.relu(bn(conv3)) + b + x ; out = relu(W_b.relu(bn(conv5)) + P)
-                if p1 is None:
-                    p1 = buf(64)
-                if last:
-                    dst, d_ctot, d_coff, s_out = hcat, 128, 64, s_hcat
-                else:
-                    s_x_new = slot()
-                    dst, d_ctot, d_coff, s_out = nxt, 64, 0, s_x_new
-                self._conv_fused(c32, halves[0], conf.shift, cat1, p1, 64, 0, cur, 64, 0, False, None, s_c1, B, H, W)
-                self._conv_fused(c52, halves[1], None, cat1, dst, d_ctot, d_coff, p1, 64, 0, True, s_out, s_c1, B, H, W)
-                if not last:
-                    s_x = s_x_new
-                    cur = nxt
-                if stages is not None:
-                    stages[f"msrb{i}"] = (hcat.clone(), 128, 64) if last else (cur.clone(), 64, 0)
-                continue
-            self._conv(c32, cat1, 128, 0, cat2, 256, 0, True, B, H, W, amax_in=s_c1, amax_out=s_c2)
-            self._conv(c52, cat1, 128, 0, cat2, 256, 128, True, B, H, W, amax_in=s_c1, amax_out=s_c2)
-            if last:   # pattern feature lands in channels [64,128) of the head input (cat: force first)
-                self._conv(conf, cat2, 256, 0, hcat, 128, 64, True, B, H, W, res=cur, r_ctot=64, r_coff=0,
-                           amax_in=s_c2, amax_out=s_hcat)
-            else:
-                s_x = slot()
-                self._conv(conf, cat2, 256, 0, nxt, 64, 0, True, B, H, W, res=cur, r_ctot=64, r_coff=0,
-                           amax_in=s_c2, amax_out=s_x)
-                cur = nxt
+                dst, s_out = (nxt, 64, 0), slot()
+            _run_msrb(p, prof, cur, s_x, *dst, s_out, ws, slot, B, H, W)
             if stages is not None:
-                stages[f"msrb{i}"] = (hcat.clone(), 128, 64) if last else (cur.clone(), 64, 0)
-        del cat1, cat2
+                stages[f"msrb{i}"] = (dst[0].clone(),) + dst[1:]
+            cur, nxt, s_x = nxt, cur, s_out
+        del ws
         # force branch
         f0, f1 = buf(64), buf(64)
         s_f = slot()
@@ -628,23 +631,16 @@ class TactileSR(nn.Module):
         if n_res == 0:
             call("tsr_cb16_to_nchw", ptr(f0), ptr(f1), _I(B), _I(64), _I(HW), _I(64), _I(0), stream())
             call("tsr_nchw_to_cb16", ptr(f1), ptr(hcat), _I(B), _I(64), _I(HW), _I(128), _I(0), stream())
-        f2 = buf(64) if n_res > 1 else None
-        curf = f0
-        for i, (c1, c2) in enumerate(plan["res"]):
-            last = i == n_res - 1
-            s_f1 = slot()
-            self._conv(c1, curf, 64, 0, f1, 64, 0, True, B, H, W, amax_in=s_f, amax_out=s_f1)
-            if last:
-                self._conv(c2, f1, 64, 0, hcat, 128, 0, True, B, H, W, res=curf, r_ctot=64, r_coff=0,
-                           amax_in=s_f1, amax_out=s_hcat)
+        cur, nxt = f0, (buf(64) if n_res > 1 else None)
+        for i, p in enumerate(plan["res"]):
+            if i == n_res - 1:
+                dst, s_out = (hcat, 128, 0), s_hcat
             else:
-                nxt = f2 if curf is f0 else f0
-                s_f = slot()
-                self._conv(c2, f1, 64, 0, nxt, 64, 0, True, B, H, W, res=curf, r_ctot=64, r_coff=0,
-                           amax_in=s_f1, amax_out=s_f)
-                curf = nxt
+                dst, s_out = (nxt, 64, 0), slot()
+            _run_res(p, prof, cur, s_f, *dst, s_out, f1, slot, B, H, W)
+            cur, nxt, s_f = nxt, cur, s_out
         h0 = buf(128)
-        self._conv(plan["head0"], hcat, 128, 0, h0, 128, 0, True, B, H, W, amax_in=s_hcat, amax_out=None)
+        _conv(prof, plan["head0"], hcat, 128, 0, h0, 128, 0, True, B, H, W, amax_in=s_hcat, amax_out=None)
         if stages is not None:
             stages["force"] = (hcat, 128, 0)
             stages["head0"] = (h0, 128, 0)
@@ -749,15 +745,15 @@ class TactileSRCNN(nn.Module):
         return f"arithmetic: eval conv_impl={self.conv_impl!r} (train mode not available)"
 
     def _get_plan(self):
-        key = (self.conv_impl, _lib.param_epoch()) + tuple((t.data_ptr(), t._version) for t in
-                                                           list(self.input_zyx.parameters()) + list(self.input_zyx.buffers())
-                                                           + list(self.output.parameters()))
+        key = (self.conv_impl, _lib.param_epoch()) + tuple((t.data_ptr(), t._version)
+                                                           for t in list(self.parameters()) + list(self.buffers()))
         if self._plan is None or key != self._plan_key:
             ns = CONV_IMPLS[self.conv_impl]
             z = self.input_zyx
             s1, sh1 = _fold(None, z[1], 64, z[0].weight.device)
             self._plan = (z[0].weight.detach().float().contiguous(), s1, sh1, _PackedConv(z[3], z[4], ns),
-                          _PackedConv(z[6], z[7], ns), self.output[0].weight.detach().float().contiguous())
+                          _PackedConv(z[6], z[7], ns), [_msrb_plan(blk, ns, True, True, False) for blk in self.msrb_layer],
+                          self.output[0].weight.detach().float().contiguous())
             self._plan_key = key
         return self._plan
 
@@ -774,24 +770,22 @@ class TactileSRCNN(nn.Module):
         assert x.dim() == 4 and x.shape[1] == 3, "TactileSRCNN takes (B, 3, h, w) taxel frames"
         x = x.detach().float().contiguous()
         with torch.no_grad():
-            w1, s1, sh1, pc2, pc3, wh = self._get_plan()
+            w1, s1, sh1, pc2, pc3, msrbs, wh = self._get_plan()
             B, _, hin, win = x.shape
             H, W = hin * 10, win * 10
-            dev = x.device
-            f16 = CONV_IMPLS[self.conv_impl] == -2
-            am = torch.zeros(4 + len(self.msrb_layer), dtype=torch.float32, device=dev) if f16 else None
-            sl = [am[i:i + 1] for i in range(am.numel())] if f16 else [None] * (4 + len(self.msrb_layer))
-            a, b = (torch.empty(B * 64 * H * W, dtype=torch.float32, device=dev) for _ in range(2))
-            call("tsr_stem_fwd", ptr(x), _I(3), _I(0), _I(3), _I(hin), _I(win), _I(10), ptr(w1), ptr(s1), ptr(sh1), ptr(a),
-                 _I(64), _I(0), _I(1), _I(B), ptr(sl[0]), stream())
-            TactileSR._conv(self, pc2, a, 64, 0, b, 64, 0, True, B, H, W, amax_in=sl[0], amax_out=sl[1])
-            TactileSR._conv(self, pc3, b, 64, 0, a, 64, 0, True, B, H, W, amax_in=sl[1], amax_out=sl[2])
-            cur, s_cur = a, sl[2]
-            del b
-            for i, blk in enumerate(self.msrb_layer):
-                blk.conv_impl = self.conv_impl
-                cur = blk._eval_cb16(cur, B, H, W, s_cur, sl[3 + i])
-                s_cur = sl[3 + i]
+            dev, prof = x.device, self._profile
+            slot = _SlotPool(3 + 3 * len(msrbs), dev, CONV_IMPLS[self.conv_impl] == NS_F16X3)
+            s_a, s_b, s_cur = slot(), slot(), slot()
+            cur, nxt = (torch.empty(B * 64 * H * W, dtype=torch.float32, device=dev) for _ in range(2))
+            call("tsr_stem_fwd", ptr(x), _I(3), _I(0), _I(3), _I(hin), _I(win), _I(10), ptr(w1), ptr(s1), ptr(sh1), ptr(cur),
+                 _I(64), _I(0), _I(1), _I(B), ptr(s_a), stream())
+            _conv(prof, pc2, cur, 64, 0, nxt, 64, 0, True, B, H, W, amax_in=s_a, amax_out=s_b)
+            _conv(prof, pc3, nxt, 64, 0, cur, 64, 0, True, B, H, W, amax_in=s_b, amax_out=s_cur)
+            ws = _msrb_workspace(msrbs[0].halves is not None, cur, B * H * W)
+            for p in msrbs:
+                s_out = slot()
+                _run_msrb(p, prof, cur, s_cur, nxt, 64, 0, s_out, ws, slot, B, H, W)
+                cur, nxt, s_cur = nxt, cur, s_out
             out = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
             call("tsr_head_fwd", ptr(cur), _I(64), _I(64), ptr(wh), ptr(out), _I(1), _I(B), _I(H), _I(W), stream())
             return out

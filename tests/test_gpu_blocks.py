@@ -69,6 +69,27 @@ def test_standalone_resblock_eval_forward(impl):
         blk(x)
 
 
+@pytest.mark.parametrize("impl", ["fp16x3", "bf16x6", "f32"])
+def test_standalone_msrb_runs_the_network_block_code(impl):
+    """Block 0 of a TactileSR and a standalone MSRB holding the same state_dict issue the same launches: fed the network's
+    own `fuse` activation, the module reproduces `stages["msrb0"]` bit for bit (under fp16x3 both sides use the stage-1
+    pair kernel and the fused 1x1; max|x| of the network's tensor comes from the producer's epilogue, the module's from a
+    reduction over the same values)."""
+    import tactilesr_amd
+    torch.manual_seed(21)
+    net = tactilesr_amd.TactileSR(patternFeatureExtraLayerCnt=2)
+    _randomise(net, 22)
+    net = net.cuda().eval()
+    net.conv_impl = impl
+    LR = (torch.rand(3, 3, 4, 4, generator=torch.Generator().manual_seed(23)) * 8).cuda()
+    _, stages = net.forward_with_stages(LR)
+    blk = tactilesr_amd.MSRB()
+    blk.load_state_dict(net.patternFeatureExtra_layer[0].state_dict())
+    blk = blk.cuda().eval()
+    blk.conv_impl = impl
+    assert torch.equal(blk(stages["fuse"]), stages["msrb0"])
+
+
 def _block_train_check(kind, B, H, W, seed):
     """Train-mode forward (batch statistics, running-stat update) and backward (input + every parameter) of a standalone
     block against torch autograd on the CPU oracle in fp64, gradients evaluated on the device's own ReLU pattern
