@@ -267,7 +267,13 @@ int tsr_pack_conv_weight_dgrad_f16s_dev(const float* w_oihw, void* w_packed, int
 /* Weight (and bias) gradient partials: slab[s][cout][cin][k][k] (s < nsplit, OIHW) with
  * dW = sum_s slab[s] (tsr_reduce_splits), from a = conv input (CB16, optional relu(a*scale+shift)
  * transform) and dz = gradient w.r.t. the conv output (CB16).  cin, cout multiples of 64.
- * bias_slab[s][cout] (optional) receives sum over pixels of dz. */
+ * bias_slab[s][cout] (optional, NULL = no bias gradient) receives sum over pixels of dz.
+ * Split s sums a contiguous range of ceil(items / nsplit) work items, items = (image, patch) pairs: 8 x 8 patches here, 4-row x
+ * 8-column ones in tsr_conv2d_wgrad_bf16s.  Any nsplit >= 1 is valid: a split whose range is empty -- nsplit above the item
+ * count, or a last split the rounded-up range leaves nothing for -- still WRITES its partial (and bias partial), as exact
+ * zeros, so tsr_reduce_splits over all nsplit partials is always right and a slab needs no clearing.  Partials are
+ * deterministic (fixed summation order, no float atomics).  A rejected call (status 1) launches nothing and leaves slab /
+ * bias_slab untouched. */
 int tsr_conv2d_wgrad(const float* a, int a_ctot, int a_coff, int cin,
                      const float* a_scale, const float* a_shift,
                      const float* dz, int dz_ctot, int dz_coff, int cout, int ks,
@@ -285,7 +291,10 @@ int tsr_conv2d_wgrad_bf16s(const float* a, int a_ctot, int a_coff, int cin,
                            float* slab, float* bias_slab, int nsplit, int B, int H, int W, void* stream);
 /* Batch splits to launch tsr_conv2d_wgrad_bf16s with (slab / bias_slab hold that many partials): one resident round
  * of workgroups for this layer shape, never more than there are (image, 4x8 patch) work items; and the number of
- * workgroups one split launches. */
+ * workgroups one split launches (grid / nsplit of the launch: kernel-row groups x C_out tiles x C_in tiles of the tile the
+ * launcher picks for (cout, cin, ks, planes)).  splits = clamp(slots / wgs_per_split, 1, B * ceil(H/4) * ceil(W/8)) with
+ * slots = 256 for the 8-wave tiles and 512 for the 4-wave ones.  Both are host arithmetic, defined for the shapes
+ * tsr_conv2d_wgrad_bf16s accepts (cout, cin multiples of 64; ks 1 / 3 / 5; planes 3 / 1 / -2 / -1). */
 int tsr_conv2d_wgrad_splits(int cout, int cin, int ks, int planes, int B, int H, int W);
 int tsr_conv2d_wgrad_wgs_per_split(int cout, int cin, int ks, int planes);
 int tsr_reduce_splits(const float* slab, float* out, long long n, int nsplit, float alpha, void* stream);

@@ -417,3 +417,56 @@ def test_conv_slab_entry_counts_follow_the_images_per_workgroup_of_each_form():
                         assert got == ((B + img - 1) // img) * tiles * img, (B, H, W, cout, ks, ns, got)
                         if img == 2:
                             assert got == lib.tsr_conv2d_slab_entries(B, H, W)
+
+
+def _engine_wgrad_shapes():
+    """(cout, cin, ks) of every nn.Conv2d of TactileSR whose weight gradient goes through tsr_conv2d_wgrad[_bf16s]: all but
+    the 3 -> 64 stems (tsr_stem_wgrad) and the 128 -> 1 head (tsr_head_bwd)."""
+    import tactilesr_amd
+    convs = [m for m in tactilesr_amd.TactileSR().modules() if isinstance(m, torch.nn.Conv2d)]
+    shapes = {(m.out_channels, m.in_channels, m.kernel_size[0]) for m in convs}
+    other = {s for s in shapes if s[0] % 64 or s[1] % 64}
+    assert other and all(cin == 3 or cout == 1 for cout, cin, _ in other), other
+    assert all(m.kernel_size[0] == m.kernel_size[1] and m.kernel_size[0] in (1, 3, 5) for m in convs)
+    return sorted(shapes - other)
+
+
+def _wgrad_grid_per_split(cout, cin, ks, planes):
+    """(workgroups one batch split launches, 8-wave tile?) restated from csrc/wgrad_mfma_tr16.hip (tr16_big, WgradTCfg,
+    launch_tr16) and csrc/wgrad_b16k.hip: grid / nsplit = kernel-row groups x C_out tiles x C_in tiles."""
+    if planes == -1 and ks == 1 and cout == 64 and cin % 256 == 0:
+        return cin // 256, True                      # streaming 1x1: one 64 x 256 workgroup (8 waves) per 256 input channels
+    if planes == 3:                                  # bf16x6: one kernel row per workgroup, 128 x 64 or 64 x 64
+        khw_big, ci_big, khw_small = 1, 64, 1
+    else:                                            # one- and two-plane forms
+        khw_big, ci_big = (3, 64) if ks == 3 else (1, 128)
+        khw_small = {1: 1, 3: 3, 5: 2}[ks]
+    if cout % 128 == 0 and cin % ci_big == 0:        # tr16_big
+        return -(-ks // khw_big) * (cout // 128) * (cin // ci_big), True
+    return -(-ks // khw_small) * (cout // 64) * (cin // 64), False
+
+
+def test_wgrad_split_helpers_follow_their_contract():
+    """include/tactilesr_hip.h: tsr_conv2d_wgrad_splits = one resident round of workgroups -- 256 slots for the 8-wave
+    (512-thread) tiles, 512 for the 4-wave ones -- never more than there are (image, 4 x 8 patch) work items, at least 1;
+    tsr_conv2d_wgrad_wgs_per_split = the launch's grid / nsplit.  Host arithmetic only: no device is touched."""
+    from tactilesr_amd import _lib
+    lib = _lib.load()
+    shapes = _engine_wgrad_shapes()
+    assert {(64, 64, 3), (64, 64, 5), (128, 128, 3), (128, 128, 5), (64, 256, 1)} <= set(shapes)
+    seen_big = set()
+    for cout, cin, ks in shapes:
+        for planes in (3, 1, -2, -1):
+            wgs, big = _wgrad_grid_per_split(cout, cin, ks, planes)
+            assert lib.tsr_conv2d_wgrad_wgs_per_split(cout, cin, ks, planes) == wgs, (cout, cin, ks, planes)
+            seen_big.add(big)
+            budget = 256 if big else 512
+            for B in (1, 2, 32, 2048):
+                for H, W in ((40, 40), (100, 100), (5, 3)):
+                    items = B * ((H + 3) // 4) * ((W + 7) // 8)
+                    ns = lib.tsr_conv2d_wgrad_splits(cout, cin, ks, planes, B, H, W)
+                    where = (cout, cin, ks, planes, B, H, W, ns)
+                    assert 1 <= ns <= items, where
+                    assert ns == 1 or ns * wgs <= budget, where
+                    assert ns == max(1, min(items, budget // wgs)), where       # and no smaller than the round allows
+    assert seen_big == {True, False}
