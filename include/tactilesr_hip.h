@@ -186,15 +186,25 @@ int tsr_head_fwd_b16(const void* in_bf16, int in_ctot, int cin, const float* w_o
 /* nn.Upsample(scale_factor=sf, bilinear, align_corners=False) + Conv2d(3->64, 3x3, pad 1, no bias)
  * + scale/shift + optional ReLU: the pattern stem's first conv (model/tactileSR_model.py:34-39)
  * and the force stem (:59-63).  lr is the NCHW taxel tensor (B, lr_ctot, hin, win); channels
- * [lr_coff, lr_coff+3) are read (the x[:, 3t:3t+3] slices of :71-78).  Output CB16, H = hin*sf. */
+ * [lr_coff, lr_coff+3) are read (the x[:, 3t:3t+3] slices of :71-78).  Output CB16, H = hin*sf, W = win*sf.
+ * hin and win are free (any taxel grid >= 1 x 1, a one-row image included); axis_cnt must be 3; scale and shift may be NULL
+ * independently (1 and 0).  Images are cut into row bands so that one band (+ halo) of the upsampled image fits in LDS;
+ * status 1 only when a band of two rows -- four padded rows of 3 x (((W + 3) & ~3) + 2) floats plus the taxels -- exceeds
+ * 32 KB: W > 676 on 4 x 4 and on 1 x 4 taxels, i.e. sf > 169 (no TactileSR shape).  Every other bad argument (a NULL tensor, B, hin, win
+ * or sf <= 0, out_ctot or out_coff not a multiple of 16, a slice that leaves [0, out_ctot) or [0, lr_ctot)) is status 1 too;
+ * a refused call launches nothing. */
 int tsr_stem_fwd(const float* lr, int lr_ctot, int lr_coff, int axis_cnt, int hin, int win, int sf,
                  const float* w_oihw, const float* scale, const float* shift,
                  float* out, int out_ctot, int out_coff, int relu, int B, float* out_amax, void* stream);
-/* out_amax (optional device scalar): receives max|output| by atomic max -- the fp16-split convolution that
- * consumes the tensor derives its power-of-two input scale from it. */
+/* out_amax (optional device scalar): receives max|output| over the finite outputs (after the affine and the ReLU; NaN
+ * outputs are skipped, a wave that holds an Inf publishes nothing) by atomic max -- the fp16-split convolution that
+ * consumes the tensor derives its power-of-two input scale from it.  The slot is only ever RAISED: the caller presets it
+ * (0, or the maximum so far), a value above the launch's own maximum is left as it was. */
 
 /* Conv2d(cin->1, 3x3, pad 1, no bias) + ReLU, CB16 in, NCHW (B,1,H,W) out: output_layer[2:]
- * (model/tactileSR_model.py:55-56).  The trailing same-size F.interpolate (:83) is an identity. */
+ * (model/tactileSR_model.py:55-56).  The trailing same-size F.interpolate (:83) is an identity.  Channels [0, cin) of the
+ * in_ctot-channel input are read; cin and in_ctot multiples of 16, B, H, W > 0 (tsr_head_fwd_b16 alike): anything else is
+ * status 1 before any launch. */
 int tsr_head_fwd(const float* in, int in_ctot, int cin, const float* w_oihw, float* out_nchw,
                  int relu, int B, int H, int W, void* stream);
 
@@ -377,7 +387,9 @@ int tsr_adam_l2_step(float* param, const float* grad, float* exp_avg, float* exp
                      float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
 /* The same step for MANY tensors in one launch (the reference's optim.Adam over all 124 parameter tensors,
  * train/tactileSR_train.py:212; cpu/trainer.py:361): `chunks` is a DEVICE array of n_chunks records, one per
- * <= 4096-element piece of a tensor, pointers already offset to the piece.  Same arithmetic as tsr_adam_l2_step. */
+ * <= 4096-element piece of a tensor, pointers already offset to the piece.  The same formula as tsr_adam_l2_step, not the
+ * same bits: the two kernels are compiled separately and the multiply-adds of the moment updates are fused in one and not
+ * in the other, so exp_avg, exp_avg_sq and the parameter can differ in the last bit between the two forms. */
 typedef struct tsr_adam_chunk {
   float* param; const float* grad; float* exp_avg; float* exp_avg_sq;
   int n; int reserved;

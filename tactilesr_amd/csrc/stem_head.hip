@@ -163,7 +163,8 @@ static int stem_fwd_impl(const float* lr, int lr_ctot, int lr_coff, int axis_cnt
                          float* out, int out_ctot, int out_coff, int relu, int B, float* out_amax, void* stream,
                          bool out16) {
   if (!lr || !w_oihw || !out || B <= 0 || axis_cnt != 3 || hin <= 0 || win <= 0 || sf <= 0) return TSR_ERR_ARG;
-  if ((out_ctot & 15) || (out_coff & 15) || out_coff + 64 > out_ctot || lr_coff + axis_cnt > lr_ctot)
+  if ((out_ctot & 15) || (out_coff & 15) || out_coff < 0 || out_coff + 64 > out_ctot || lr_coff < 0 ||
+      lr_coff + axis_cnt > lr_ctot)
     return TSR_ERR_ARG;
   const int H = hin * sf, W = win * sf;
   const int WP = ((W + 3) & ~3) + 2;
@@ -172,7 +173,7 @@ static int stem_fwd_impl(const float* lr, int lr_ctot, int lr_coff, int axis_cnt
   const size_t fixed = (size_t)((3 * hin * win + 3) & ~3) * 4;
   int RB = 0;
   double best = -1.0;
-  for (int rb = 2; rb <= H; ++rb) {
+  for (int rb = 2; rb <= (H < 2 ? 2 : H); ++rb) {      // (a one-row image still gets the smallest band)
     if (fixed + (size_t)3 * (rb + 2) * WP * 4 > 32 * 1024) break;
     long items = 0, slots = 0;
     for (int y = 0; y < H; y += rb) {
@@ -323,7 +324,8 @@ static int head_launch(const float* in, int in_ctot, int cin, const float* w_oih
 
 extern "C" int tsr_head_fwd(const float* in, int in_ctot, int cin, const float* w_oihw, float* out_nchw,
                             int relu, int B, int H, int W, void* stream) {
-  if (!in || !w_oihw || !out_nchw || B <= 0 || (cin & 15) || (in_ctot & 15) || cin > in_ctot || cin <= 0)
+  if (!in || !w_oihw || !out_nchw || B <= 0 || H <= 0 || W <= 0 || (cin & 15) || (in_ctot & 15) || cin > in_ctot ||
+      cin <= 0)
     return TSR_ERR_ARG;
   return head_launch<false>(in, in_ctot, cin, w_oihw, out_nchw, relu, B, H, W, stream);
 }
@@ -432,7 +434,8 @@ static int head_mfma_launch(const void* in, int in_ctot, int cin, const float* w
 // bf16 activation storage: `in` is bf16 CB16; the image comes out fp32 NCHW as always
 extern "C" int tsr_head_fwd_b16(const void* in_bf16, int in_ctot, int cin, const float* w_oihw, float* out_nchw,
                                 int relu, int B, int H, int W, void* stream) {
-  if (!in_bf16 || !w_oihw || !out_nchw || B <= 0 || (cin & 15) || (in_ctot & 15) || cin > in_ctot || cin <= 0)
+  if (!in_bf16 || !w_oihw || !out_nchw || B <= 0 || H <= 0 || W <= 0 || (cin & 15) || (in_ctot & 15) || cin > in_ctot ||
+      cin <= 0)
     return TSR_ERR_ARG;
   if (cin == 128 || cin == 64) {
     const int st = head_mfma_launch(in_bf16, in_ctot, cin, w_oihw, out_nchw, relu, B, H, W, stream);

@@ -341,3 +341,78 @@ def test_tpsf_clipped_step_is_torchs():
         assert _same(p.detach(), q.detach()) and _same(p.grad, q.grad), n
         for k in ("exp_avg", "exp_avg_sq"):
             assert _same(oa.state[p][k], ot.state[q][k]), (n, k)
+
+
+# ------------------------------------------------------------------------------------- tsr_adam_l2_step, the one-tensor form
+def _f32(x):
+    """x rounded to float, as a Python double: what a `float` argument of the C ABI receives."""
+    return torch.tensor(x, dtype=torch.float32).item()
+
+
+ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS, ADAM_WD = _f32(1e-3), _f32(0.9), _f32(0.999), _f32(1e-8), _f32(1e-2)
+ADAM_GUARD = 8
+
+
+def _adam_state(n, step):
+    g = torch.Generator().manual_seed(n % 1000 + step)
+    p, gr = torch.randn(n, generator=g), torch.randn(n, generator=g) * 1e-2
+    if step == 1:
+        m, v = torch.zeros(n), torch.zeros(n)
+    else:        # a state as earlier steps leave it: sqrt(v) well above |m| / 50, so the update stays of the order of lr
+        m, v = torch.randn(n, generator=g) * 1e-2, torch.rand(n, generator=g) * 1e-2 + 1e-3
+    return p, gr, m, v
+
+
+def _guarded(t):
+    return torch.cat([t, torch.full((ADAM_GUARD,), float("nan"))]).cuda()
+
+
+@pytest.mark.parametrize("step", [1, 2, 1000])
+@pytest.mark.parametrize("n", [1, 4095, 4097, 4096 * 256 + 7])
+def test_adam_l2_step_one_tensor_form_vs_fp64_and_the_multi_form(n, step):
+    """tsr_adam_l2_step (grid-stride, 4096 x 256 threads: n = 4096 * 256 + 7 takes a second trip) and tsr_adam_l2_multi
+    on the same data cut into chunks of at most 4096, the multi form handed the float-rounded betas as doubles.
+
+    The two are NOT bit-identical: they are the same formula, but the compiler fuses b1 * m + (1 - b1) * g' and
+    b2 * v + ((1 - b2) g') g' into multiply-adds in the multi form's 16-byte path and leaves them as separate roundings
+    in the one-tensor kernel (read off the gfx950 assembly), a legitimate last-bit difference.  Both are therefore held
+    to fp64 Adam (the oracle's adam_l2_step) at the 1e-5 bar this file uses for the moments, per tensor, for the
+    parameter and both moments.  (No tighter bar on the parameter: at step 1 the update lr * g' / (|g'| + eps') is
+    ill-conditioned where g' = g + wd * w cancels to about eps, whatever the arithmetic.)"""
+    import ctypes
+    from tactilesr_amd._lib import call, ptr, stream, c_int as I, c_float as Fl, c_longlong as L
+    p, gr, m, v = _adam_state(n, step)
+    ref = {"w": p.double()}
+    state = {"w": {"m": m.double(), "v": v.double()}}
+    O.adam_l2_step(ref, {"w": gr.double()}, state, step, ADAM_LR, ADAM_WD, (ADAM_B1, ADAM_B2), ADAM_EPS)
+    want = dict(param=ref["w"], exp_avg=state["w"]["m"], exp_avg_sq=state["w"]["v"])
+
+    one = [_guarded(t) for t in (p, gr, m, v)]
+    call("tsr_adam_l2_step", *[ptr(t) for t in one], L(n), Fl(ADAM_LR), Fl(ADAM_B1), Fl(ADAM_B2), Fl(ADAM_EPS), Fl(ADAM_WD),
+         I(step), stream())
+    multi = [_guarded(t) for t in (p, gr, m, v)]
+    recs = [tuple(t.data_ptr() + 4 * off for t in multi) + (min(optim.CHUNK, n - off), 0) for off in range(0, n, optim.CHUNK)]
+    arr = (optim._Rec * len(recs))(*recs)
+    table = torch.frombuffer(memoryview(arr).cast("B"), dtype=torch.uint8).clone().cuda()
+    call("tsr_adam_l2_multi", ptr(table), I(len(recs)), Fl(ADAM_LR), ctypes.c_double(ADAM_B1), ctypes.c_double(ADAM_B2),
+         Fl(ADAM_EPS), Fl(ADAM_WD), I(step), stream())
+    torch.cuda.synchronize()
+    for form, bufs in (("one-tensor", one), ("multi", multi)):
+        got = dict(param=bufs[0].cpu(), exp_avg=bufs[2].cpu(), exp_avg_sq=bufs[3].cpu())
+        assert torch.equal(bufs[1].cpu()[:n], gr), f"{form}: the gradient was written"
+        for k, t in got.items():
+            assert torch.isnan(t[n:]).all(), f"{form}: wrote behind {k}"
+            err = float((t[:n].double() - want[k]).abs().max())
+            rel = err / float(want[k].abs().max())
+            print(f"[adam {form} n={n} step={step}] {k} {rel:.2e}")
+            assert rel <= 1e-5, (form, k, rel)
+
+
+@pytest.mark.parametrize("n,step", [(0, 1), (-5, 1), (16, 0), (16, -1)])
+def test_adam_l2_step_rejects_empty_tensors_and_step_zero(n, step):
+    from tactilesr_amd._lib import load, ptr, stream, c_int as I, c_float as Fl, c_longlong as L
+    bufs = [torch.full((16,), float("nan"), device="cuda") for _ in range(4)]
+    st = load().tsr_adam_l2_step(*[ptr(t) for t in bufs], L(n), Fl(ADAM_LR), Fl(ADAM_B1), Fl(ADAM_B2), Fl(ADAM_EPS), Fl(ADAM_WD),
+                                 I(step), stream())
+    torch.cuda.synchronize()
+    assert st == 1 and all(torch.isnan(t).all() for t in bufs)

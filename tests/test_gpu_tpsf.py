@@ -1,5 +1,7 @@
 """GPU parity of the batched tPSFNet path against the reference's own outputs (tests/golden/tpsf.npz:
 forward 4-tuple, trainer loss, MLP gradients)."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -331,3 +333,61 @@ def test_seqs_dataset_generator_matches_the_batch1_loop(tmp_path):
     ds = np.load(path, allow_pickle=True)
     assert len(ds) == len(out["train"]) and np.ascontiguousarray(ds[1].item()["LR"]).shape == (21, 4, 4)
     assert np.ascontiguousarray(ds[1].item()["HR"]).shape == (1, 100, 100)
+
+
+ACT_GUARD = 8
+
+
+def _act_buffers(n, seed):
+    """dy (randn) and y with NaN guard elements behind them; y log-spaced over 1e-7 .. 30 in shuffled order, every
+    fourth element negated or zeroed for the ReLU mode."""
+    g = torch.Generator().manual_seed(seed)
+    dy = torch.randn(n, generator=g)
+    y = torch.logspace(-7, math.log10(30.0), n, dtype=torch.float64)[torch.randperm(n, generator=g)].float()
+    guard = torch.full((ACT_GUARD,), float("nan"))
+    return dy, y, torch.cat([dy, guard]).cuda(), torch.cat([y, guard]).cuda()
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 4096 * 256 + 5])
+def test_act_bwd_relu_is_exact(n):
+    """tsr_act_bwd mode 1: dy where y > 0, else 0, bit for bit; n = 4096 * 256 + 5 takes the grid-stride loop round twice."""
+    from tactilesr_amd._lib import call, ptr, stream, c_int as I, c_longlong as L
+    dy, y, dy_d, y_d = _act_buffers(n, 11 + n % 97)
+    y[1::4] = -y[1::4]
+    y[3::4] = 0.0
+    y_d[:n] = y.cuda()
+    call("tsr_act_bwd", ptr(dy_d), ptr(y_d), L(n), I(1), stream())
+    got = dy_d.cpu()
+    assert torch.isnan(got[n:]).all()
+    assert torch.equal(got[:n], torch.where(y > 0, dy, torch.zeros(())))
+    assert n < 4 or bool((got[:n] == 0).any())
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 4096 * 256 + 5])
+def test_act_bwd_softplus_small_outputs_keep_their_precision(n):
+    """tsr_act_bwd mode 2: dy * (1 - exp(-y)) from the stored Softplus output y over 1e-7 .. 30, element by element against
+    fp64 with a RELATIVE error of at most 1e-6 each (a few fp32 ulps of expm1 and one multiply; a 1 - expf(-y) form loses
+    every digit at the small end: its error there exceeds 1e-1)."""
+    from tactilesr_amd._lib import call, ptr, stream, c_int as I, c_longlong as L
+    dy, y, dy_d, y_d = _act_buffers(n, 23 + n % 97)
+    call("tsr_act_bwd", ptr(dy_d), ptr(y_d), L(n), I(2), stream())
+    got = dy_d.cpu()
+    assert torch.isnan(got[n:]).all()
+    ref = dy.double() * -torch.expm1(-y.double())
+    err = (got[:n].double() - ref).abs()
+    nz = ref != 0                                          # (randn yields an exact 0 now and then: 0 must stay 0)
+    print(f"[act_bwd softplus n={n}] worst element {float((err[nz] / ref[nz].abs()).max()):.2e}")
+    assert bool((err <= 1e-6 * ref.abs()).all())
+    if n > 1000:         # the bar bites: the naive form, in fp32, misses it by orders of magnitude on these inputs
+        naive = dy * (1 - torch.exp(-y))
+        assert float(((naive.double() - ref).abs()[nz] / ref[nz].abs()).max()) > 1e-1
+
+
+@pytest.mark.parametrize("mode,n", [(0, 64), (3, 64), (1, 0), (2, -1)])
+def test_act_bwd_rejects_unknown_modes_and_empty_tensors(mode, n):
+    from tactilesr_amd._lib import load, ptr, stream, c_int as I, c_longlong as L
+    dy, y, dy_d, y_d = _act_buffers(64, 5)
+    st = load().tsr_act_bwd(ptr(dy_d), ptr(y_d), L(n), I(mode), stream())
+    torch.cuda.synchronize()
+    assert st == 1
+    assert torch.equal(dy_d.cpu()[:64], dy) and torch.isnan(dy_d.cpu()[64:]).all()
