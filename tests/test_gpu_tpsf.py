@@ -224,8 +224,10 @@ def test_sgemm_mfma_strides_activations_and_splitk(M, N, K, act, ta, tb):
 
 def test_tpsf_kernels_wide_dynamic_range_batch():
     """MFMA Toeplitz-GEMM forward/backward (two scaled fp16 planes) against an fp64 torch restatement on inputs the
-    golden fixture does not reach: signed depth, tiny and large magnitudes, narrow and wide PSFs, 300 samples so that
-    the persistent workgroups loop."""
+    golden fixture does not reach: signed depth, tiny and large magnitudes, narrow and wide PSFs.  At 300 samples only
+    tpsf_bwd_dhb_kernel's 256 persistent workgroups loop (44 of them, over samples the fp64 subset does not include); the
+    forward (512 workgroups) and tpsf_bwd_pool_kernel (2048) do not.  Later iterations are compared with fp64 in
+    test_gpu_persistent_loops.py."""
     from tactilesr_amd._lib import call, ptr, stream, c_int as I
     B = 300
     g = torch.Generator().manual_seed(5)
