@@ -92,7 +92,29 @@ int tsr_conv2d_fwd_f16s_pair(const float* in, int in_ctot, int in_coff, int cin,
  * the kernel from the device scalar in_amax = max|x| that the producer wrote through its out_amax -- then split
  * x*sx = h1+h2, w*sw = g1+g2 (22+ significand bits) and h1g1 + h1g2 + h2g1 are accumulated in fp32; the scales
  * are undone exactly in the epilogue.  Half the MFMA work of bf16x6; network-level error equal to the reference's
- * own fp32 CPU run against fp64 (tests).  Same remaining arguments as tsr_conv2d_fwd. */
+ * own fp32 CPU run against fp64 (tests).  Same remaining arguments as tsr_conv2d_fwd.
+ *
+ * in_amax / out_amax (the three fp16x3 inference launches: tsr_conv2d_fwd_f16s, _f16s_pair, _f16s_fuse1x1; checked launch by
+ * launch in tests/test_gpu_infer_fp16x3.py):
+ *  - in_amax (required) is an UPPER BOUND of max|x| over the input slice, not necessarily the maximum.  Only its exponent
+ *    is used, sx = 2^(13 - floor(log2 in_amax)): two bounds of one binade give bit-identical results.  A bound 2^j times the
+ *    true maximum costs at most j low bits of the activation planes: the error against fp64 stays below 2^j times the bar
+ *    of the exact bound (measured for j = 1, 2: unchanged).  in_amax = 0 (an all-zero input) gives sx = 1 and exactly
+ *    act(shift + res).
+ *  - every scale is a power of two and is undone exactly: x * 2^k with in_amax * 2^k (power-of-two `scale`, no shift / res)
+ *    gives exactly 2^k times the output and out_amax, as long as the input, the output and the factor the accumulator is
+ *    multiplied by, w_inv_scale / sx = 2^(floor(log2 max|w|) + floor(log2 in_amax) - 26), stay normal fp32 numbers; sx itself
+ *    is clamped to [2^-126, 2^127].  Held by the tests for |k| <= 60 on inputs of magnitude ~10.
+ *  - out_amax (optional, NULL = off) follows the rule stated at tsr_stem_fwd: the slot is only ever RAISED by atomic max; the
+ *    caller presets it (0, or the maximum so far -- two launches may share a slot), a prior above the launch's own maximum
+ *    survives bit for bit, a prior below it ends as max|out| over the launch's output slice exactly.
+ * Refusals (status 1, nothing is launched, `out` and `out_amax` are untouched) of the three launches: a NULL in, w_packed,
+ * out or in_amax (fuse1x1: or w2_packed); B, H or W <= 0; cin <= 0; cin, any ctot or any coff not a multiple of 16; a negative
+ * coff or a slice that leaves its buffer (coff + channels > ctot) for in, out and -- when res is given -- res; w_inv_scale
+ * (fuse1x1: or w2_inv_scale) <= 0 or NaN; cout not in {64, 128}; ks not in {1, 3, 5} (fuse1x1: not in {3, 5}).  scale, shift,
+ * res, shift2 and out_amax may each be NULL on their own (1 / 0 / no residual / 0 / off).  The pack routines refuse a NULL
+ * weight or w_packed (_dev: or w_amax), cin <= 0 or not a multiple of 16, cout not in {64, 128}, ks not in {1, 3, 5} and a
+ * wscale <= 0 or NaN (tsr_pack_conv_weight_pair_f16s: only when w_amax is NULL, which otherwise replaces wscale). */
 int tsr_pack_conv_weight_f16s(const float* w_oihw, void* w_packed, int cout, int cin, int ks, float wscale,
                               void* stream);
 /* Same with the scale derived ON THE DEVICE from w_amax[0] = max|w| (a device scalar the caller computed without a host

@@ -635,7 +635,7 @@ extern "C" int tsr_conv2d_fwd_f16s_pair(const float* in, int in_ctot, int in_cof
                                         int relu, int B, int H, int W, void* stream) {
   if (!in || !w_packed || !out || !in_amax || B <= 0 || H <= 0 || W <= 0 || !(w_inv_scale > 0.f)) return TSR_ERR_ARG;
   if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff + cin > in_ctot || out_coff + 128 > out_ctot)
+      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + 128 > out_ctot)
     return TSR_ERR_ARG;
   ConvArgs a = {};
   a.in = in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;

@@ -561,7 +561,7 @@ extern "C" int tsr_pack_conv_weight_bf16s(const float* w_oihw, void* w_packed, i
 // max|w|*wscale lies in [2^13, 2^14)); tsr_conv2d_fwd_f16s gets 1/wscale back.
 extern "C" int tsr_pack_conv_weight_f16s(const float* w_oihw, void* w_packed, int cout, int cin, int ks,
                                          float wscale, void* stream) {
-  if (!w_oihw || !w_packed || (cin & 15) || (cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5) ||
+  if (!w_oihw || !w_packed || cin <= 0 || (cin & 15) || (cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5) ||
       !(wscale > 0.f))
     return TSR_ERR_ARG;
   const int k32 = k32_mode(ks, cin, cout);
@@ -575,7 +575,7 @@ extern "C" int tsr_pack_conv_weight_f16s(const float* w_oihw, void* w_packed, in
 
 extern "C" int tsr_pack_conv_weight_f16s_dev(const float* w_oihw, void* w_packed, int cout, int cin, int ks,
                                              const float* w_amax, void* stream) {
-  if (!w_oihw || !w_packed || !w_amax || (cin & 15) || (cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5))
+  if (!w_oihw || !w_packed || !w_amax || cin <= 0 || (cin & 15) || (cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5))
     return TSR_ERR_ARG;
   const int k32 = k32_mode(ks, cin, cout);
   const int tps = k32 ? 1 : taps_per_step(ks, cout, 2);
@@ -847,9 +847,9 @@ extern "C" int tsr_conv2d_fwd_f16s_fuse1x1(const float* in, int in_ctot, int in_
       !(w2_inv_scale > 0.f) || (ks != 3 && ks != 5))
     return TSR_ERR_ARG;
   if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff + cin > in_ctot || out_coff + 64 > out_ctot)
+      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + 64 > out_ctot)
     return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff + 64 > res_ctot)) return TSR_ERR_ARG;
+  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + 64 > res_ctot)) return TSR_ERR_ARG;
   ConvArgs a = {};
   a.in = in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
   a.wp = (const float*)w_packed; a.scale = scale; a.shift = shift; a.relu = relu;
@@ -934,10 +934,11 @@ extern "C" int tsr_conv2d_fwd_f16s(const float* in, int in_ctot, int in_coff, in
                                    float* out, int out_ctot, int out_coff, int relu,
                                    int B, int H, int W, void* stream) {
   if (!in || !w_packed || !out || !in_amax || B <= 0 || H <= 0 || W <= 0 || !(w_inv_scale > 0.f)) return TSR_ERR_ARG;
+  if ((cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5)) return TSR_ERR_ARG;
   if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff + cin > in_ctot || out_coff + cout > out_ctot)
+      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + cout > out_ctot)
     return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
+  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
   ConvArgs a = {};
   a.in = in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
   a.wp = (const float*)w_packed; a.scale = scale; a.shift = shift;
