@@ -38,7 +38,8 @@ int tsr_build_flags(void);
 
 /* Re-order an nn.Conv2d weight (OIHW fp32; Cout in {64,128}, Cin % 16 == 0, k in {1,3,5})
  * into the [Cin/16][k*k][4][Cout][4] stream order tsr_conv2d_fwd consumes.
- * w_packed holds Cout*Cin*k*k floats. */
+ * w_packed holds Cout*Cin*k*k floats.  Status 1 and no launch for a NULL pointer, cin <= 0 or a shape outside the above
+ * (tsr_pack_conv_weight_bf16s alike). */
 int tsr_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin, int ks, void* stream);
 
 /* out[:, coff:coff+cout] = act( conv2d(in[:, in_coff:in_coff+cin], W, stride 1, pad k/2) * scale + shift
@@ -50,7 +51,10 @@ int tsr_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin
  *   stem conv2 / inputContact_layer / output_layer[0]  :41-43,47-49,53-54
  * scale/shift are per-output-channel (NULL = 1 / 0): eval-mode BN folds to
  *   scale = gamma/sqrt(running_var+eps), shift = (bias-running_mean)*scale+beta.
- * in/out/res are CB16; fp32 MFMA (exact fp32 fma chain). */
+ * in/out/res are CB16; fp32 MFMA (exact fp32 fma chain).
+ * tsr_conv2d_fwd, tsr_conv2d_fwd_bf16s and tsr_conv2d_ex refuse (status 1, nothing launched) a NEGATIVE channel offset like
+ * any other slice that leaves its buffer: in_coff, out_coff and -- when the tensor is given -- res_coff (tsr_conv2d_ex: and
+ * mask_coff). */
 int tsr_conv2d_fwd(const float* in, int in_ctot, int in_coff, int cin,
                    const float* w_packed, int cout, int ks,
                    const float* scale, const float* shift,
@@ -164,7 +168,17 @@ int tsr_conv2d_fwd_b16(const void* in, int in_ctot, int in_coff, int cin, const 
  * reads and weight bytes on the 16 outer taps are skipped.  The weight layouts:
  * w_packed from tsr_pack_conv_weight_b16k ([C_in/32][tap][4][C_out][8] bf16; tsr_conv_weight_b16k_elems elements),
  * w2_packed from tsr_pack_w2_b16k (the 64x128 fp32 half of `confusion`, model/tactileSR_model.py:203-206, HALVED, in the K
- * order of the fused epilogue). */
+ * order of the fused epilogue).
+ * Refusals (status 1, nothing is launched, `out` is untouched) of tsr_conv2d_fwd_b16 and the three b16k launches (checked
+ * launch by launch in tests/test_gpu_infer_b16.py, without a device in tests/test_infer_b16_cpu.py): a NULL in, w_packed or
+ * out (fuse1x1: or w2_packed); B, H or W <= 0; cin <= 0; cin, any ctot or any coff not a multiple of 16 (the b16k forms: cin
+ * not a multiple of 32); a negative coff or a slice that leaves its buffer (coff + channels > ctot) for in, out and -- when
+ * res is given -- res; cout not in {64, 128}; ks not in {1, 3, 5} for tsr_conv2d_fwd_b16, not in {3, 5} for the b16k forms;
+ * the b16k forms: 8 * in_ctot * H * W >= 2^31 (32-bit halo offsets inside a 4-image group).  scale, shift, res and shift2
+ * may each be NULL on their own (1 / 0 / no residual / 0).  tsr_pack_conv_weight_b16k refuses a NULL pointer, cout not in
+ * {64, 128}, cin <= 0 or not a multiple of 32 and ks not in {3, 5} (ks = 1: cout = 64 only); _b16k_pair a NULL pointer and
+ * cin <= 0 or not a multiple of 32; tsr_pack_w2_b16k a NULL pointer.  tsr_conv_weight_b16k_elems = cout * cin * ks * ks,
+ * tsr_conv_weight_b16k_pair_elems = (cin / 32) * 17 * 4096. */
 long long tsr_conv_weight_b16k_elems(int cout, int cin, int ks);
 int tsr_pack_conv_weight_b16k(const float* w_oihw, void* w_packed, int cout, int cin, int ks, void* stream);
 int tsr_pack_w2_b16k(const float* w2_64x128, void* w_packed, void* stream);

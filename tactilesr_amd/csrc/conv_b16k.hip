@@ -864,10 +864,10 @@ static int b16k_fill(ConvArgs& a, const void* in, int in_ctot, int in_coff, int 
                      const float* scale, const float* shift, const void* res, int res_ctot, int res_coff, void* out,
                      int out_ctot, int out_coff, int out_ch, int relu, int B, int H, int W) {
   if (!in || !w_packed || !out || B <= 0 || H <= 0 || W <= 0) return TSR_ERR_ARG;
-  if ((in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || in_coff + cin > in_ctot ||
-      out_coff + out_ch > out_ctot)
+  if ((in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || in_coff < 0 || out_coff < 0 ||
+      in_coff + cin > in_ctot || out_coff + out_ch > out_ctot)
     return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff + out_ch > res_ctot)) return TSR_ERR_ARG;
+  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + out_ch > res_ctot)) return TSR_ERR_ARG;
   if ((long long)4 * in_ctot * H * W * 2 >= 0x7fffffffLL) return TSR_ERR_ARG;      // 32-bit halo offsets inside a 4-image group
   a = ConvArgs{};
   a.in = (const float*)in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;

@@ -244,7 +244,7 @@ extern "C" int tsr_pack_conv_weight_dgrad(const float* w_oihw, float* w_packed, 
 
 extern "C" int tsr_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin, int ks,
                                     void* stream) {
-  if (!w_oihw || !w_packed || (cin & 15) || (cout != 64 && cout != 128) ||
+  if (!w_oihw || !w_packed || cin <= 0 || (cin & 15) || (cout != 64 && cout != 128) ||
       (ks != 1 && ks != 3 && ks != 5))
     return TSR_ERR_ARG;
   const size_t total = (size_t)cout * cin * ks * ks;
@@ -270,7 +270,7 @@ static int dispatch_conv(const ConvArgs& a, int cout, int ks, hipStream_t st) {
 
 static int check_slices(int cin, int in_ctot, int in_coff, int cout, int out_ctot, int out_coff) {
   if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff + cin > in_ctot || out_coff + cout > out_ctot)
+      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + cout > out_ctot)
     return TSR_ERR_ARG;
   return TSR_OK;
 }
@@ -283,7 +283,7 @@ extern "C" int tsr_conv2d_fwd(const float* in, int in_ctot, int in_coff, int cin
                               int B, int H, int W, void* stream) {
   if (!in || !w_packed || !out || B <= 0 || H <= 0 || W <= 0) return TSR_ERR_ARG;
   if (check_slices(cin, in_ctot, in_coff, cout, out_ctot, out_coff)) return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
+  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
   ConvArgs a = {};
   a.in = in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
   a.wp = w_packed; a.scale = scale; a.shift = shift;
@@ -317,11 +317,11 @@ int tsr_conv2d_ex_bf16s(const ConvArgs& a, int cout, int ks, int nsplit, hipStre
 extern "C" int tsr_conv2d_ex(const tsr_conv_desc* d, void* stream) {
   if (!d || !d->in || !d->w_packed || !d->out || d->B <= 0 || d->H <= 0 || d->W <= 0) return TSR_ERR_ARG;
   if (check_slices(d->cin, d->in_ctot, d->in_coff, d->cout, d->out_ctot, d->out_coff)) return TSR_ERR_ARG;
-  if (d->res && ((d->res_ctot & 15) || (d->res_coff & 15) || d->res_coff + d->cout > d->res_ctot))
+  if (d->res && ((d->res_ctot & 15) || (d->res_coff & 15) || d->res_coff < 0 || d->res_coff + d->cout > d->res_ctot))
     return TSR_ERR_ARG;
   if (d->epi_mode < 0 || d->epi_mode > 2) return TSR_ERR_ARG;
   if (d->epi_mode == 1 && (!d->slab || !d->slab_cnt)) return TSR_ERR_ARG;
-  if (d->epi_mode == 2 && (!d->mask || (d->mask_ctot & 15) || (d->mask_coff & 15) ||
+  if (d->epi_mode == 2 && (!d->mask || (d->mask_ctot & 15) || (d->mask_coff & 15) || d->mask_coff < 0 ||
                            d->mask_coff + d->cout > d->mask_ctot || (d->bn_a && (!d->bn_b || !d->slab))))
     return TSR_ERR_ARG;
   if ((d->in_scale != nullptr) != (d->in_shift != nullptr)) return TSR_ERR_ARG;

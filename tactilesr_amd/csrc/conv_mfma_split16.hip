@@ -546,7 +546,7 @@ extern "C" long long tsr_conv_weight_bf16s_elems(int cout, int cin, int ks, int 
 
 extern "C" int tsr_pack_conv_weight_bf16s(const float* w_oihw, void* w_packed, int cout, int cin, int ks,
                                           int nsplit, void* stream) {
-  if (!w_oihw || !w_packed || (cin & 15) || (cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5) ||
+  if (!w_oihw || !w_packed || cin <= 0 || (cin & 15) || (cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5) ||
       nsplit < 1 || nsplit > 3)
     return TSR_ERR_ARG;
   const int tps = taps_per_step(ks, cout, nsplit);
@@ -817,9 +817,9 @@ extern "C" int tsr_conv2d_fwd_bf16s(const float* in, int in_ctot, int in_coff, i
                                     int B, int H, int W, void* stream) {
   if (!in || !w_packed || !out || B <= 0 || H <= 0 || W <= 0 || nsplit < 1 || nsplit > 3) return TSR_ERR_ARG;
   if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff + cin > in_ctot || out_coff + cout > out_ctot)
+      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + cout > out_ctot)
     return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
+  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
   ConvArgs a = {};
   a.in = in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
   a.wp = (const float*)w_packed; a.scale = scale; a.shift = shift;
@@ -899,10 +899,11 @@ extern "C" int tsr_conv2d_fwd_b16(const void* in, int in_ctot, int in_coff, int 
                                   void* out, int out_ctot, int out_coff, int relu,
                                   int B, int H, int W, void* stream) {
   if (!in || !w_packed || !out || B <= 0 || H <= 0 || W <= 0) return TSR_ERR_ARG;
+  if ((cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5)) return TSR_ERR_ARG;
   if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff + cin > in_ctot || out_coff + cout > out_ctot)
+      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + cout > out_ctot)
     return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
+  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
   ConvArgs a = {};
   a.in = (const float*)in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
   a.wp = (const float*)w_packed; a.scale = scale; a.shift = shift;
