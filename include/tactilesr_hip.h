@@ -39,7 +39,7 @@ int tsr_build_flags(void);
 /* Re-order an nn.Conv2d weight (OIHW fp32; Cout in {64,128}, Cin % 16 == 0, k in {1,3,5})
  * into the [Cin/16][k*k][4][Cout][4] stream order tsr_conv2d_fwd consumes.
  * w_packed holds Cout*Cin*k*k floats.  Status 1 and no launch for a NULL pointer, cin <= 0 or a shape outside the above
- * (tsr_pack_conv_weight_bf16s alike). */
+ * (tsr_pack_conv_weight_bf16s alike); the full list of refusals is in the "Refusals" paragraph at tsr_conv2d_fwd_bf16s below. */
 int tsr_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin, int ks, void* stream);
 
 /* out[:, coff:coff+cout] = act( conv2d(in[:, in_coff:in_coff+cin], W, stride 1, pad k/2) * scale + shift
@@ -54,7 +54,7 @@ int tsr_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin
  * in/out/res are CB16; fp32 MFMA (exact fp32 fma chain).
  * tsr_conv2d_fwd, tsr_conv2d_fwd_bf16s and tsr_conv2d_ex refuse (status 1, nothing launched) a NEGATIVE channel offset like
  * any other slice that leaves its buffer: in_coff, out_coff and -- when the tensor is given -- res_coff (tsr_conv2d_ex: and
- * mask_coff). */
+ * mask_coff).  Every refusal of tsr_conv2d_fwd is listed in the "Refusals" paragraph at tsr_conv2d_fwd_bf16s below. */
 int tsr_conv2d_fwd(const float* in, int in_ctot, int in_coff, int cin,
                    const float* w_packed, int cout, int ks,
                    const float* scale, const float* shift,
@@ -67,7 +67,18 @@ int tsr_conv2d_fwd(const float* in, int in_ctot, int in_coff, int cin,
  * fp32.  nsplit = 3 ("bf16x6": 6 products, 24 significand bits -> fp32-equivalent results, error <= the fp32
  * MFMA path's); nsplit = 2 ("bf16x3": 3 products, ~4e-6 per layer); nsplit = 1 (plain bf16 operands).
  * Same arguments and semantics as tsr_conv2d_fwd; weights come from tsr_pack_conv_weight_bf16s
- * (tsr_conv_weight_bf16s_elems() bf16 values: taps padded to the kernel's step size). */
+ * (tsr_conv_weight_bf16s_elems() bf16 values: taps padded to the kernel's step size).
+ * Refusals (status 1, nothing is launched, `out` is untouched) of tsr_conv2d_fwd and tsr_conv2d_fwd_bf16s (checked launch by
+ * launch in tests/test_gpu_infer_f32s.py, without a device in tests/test_infer_f32s_cpu.py): a NULL in, w_packed or out; B, H
+ * or W <= 0; cin <= 0; cin, any ctot or any coff not a multiple of 16; a negative coff or a slice that leaves its buffer
+ * (coff + channels > ctot) for in, out and -- when res is given -- res; cout not in {64, 128}; ks not in {1, 3, 5};
+ * tsr_conv2d_fwd_bf16s: nsplit not in {1, 2, 3}.  scale, shift and res may each be NULL on their own (1 / 0 / no residual;
+ * res_ctot and res_coff are then ignored).  tsr_pack_conv_weight and tsr_pack_conv_weight_bf16s refuse a NULL pointer, cin <= 0
+ * or not a multiple of 16, cout not in {64, 128}, ks not in {1, 3, 5} and (_bf16s) nsplit not in {1, 2, 3}; a refused pack
+ * leaves w_packed untouched.  tsr_pack_conv_weight_bf16s writes nsplit * cout * cin * (padded taps) elements in the order
+ * [cin/16][step][tap in step][plane][2][cout][8], plane p the bf16 of what the planes before it leave of the weight, padded
+ * tap slots zero; tsr_conv_weight_bf16s_elems may be larger (never below nsplit * cout * round_up(cin, 32) * ks * ks) and the
+ * pack leaves the surplus as it found it. */
 long long tsr_conv_weight_bf16s_elems(int cout, int cin, int ks, int nsplit);   /* bf16 elements of w_packed */
 int tsr_pack_conv_weight_bf16s(const float* w_oihw, void* w_packed, int cout, int cin, int ks, int nsplit,
                                void* stream);
