@@ -485,21 +485,39 @@ int tsr_psnr_ssim(const float* a, const float* b, int B, int n, double psnr_div,
  * reference's geometry constants are (:40-55).
  * ------------------------------------------------------------------------------------- */
 /* tactilePSF + depth2tactile + degradation_process (:78-100,129-141) from alpha_beta (B,3) =
- * (alpha, beta, gamma): HR (B,1,100,100), LR_deg (B,1,4,4), psf (B,1,99,99).  Separable form. */
+ * (alpha, beta, gamma): HR (B,1,100,100), LR_deg (B,1,4,4), psf (B,1,99,99).  Separable form.
+ * Plateau: the pixels with depth > depth.max() - 1e-3 (never empty in exact arithmetic; evaluated in fp32 like the reference,
+ * so a maximum of 2^15 or more, which 1e-3 no longer moves, has none) hold max(HR off the plateau, 0).  Degenerate
+ * plateaus follow from that: an image that is all plateau (constant depth, all zeros) gives HR = 0 and LR_deg = 0 exactly,
+ * and psf as always; when every pixel off the plateau has a negative HR the plateau holds 0.  Samples are independent: a
+ * NaN or Inf in one sample's depth or parameters stays in that sample's outputs.
+ * Refusals: a NULL depth, alpha_beta, HR, LR_deg or psf, or B <= 0, returns status 1, launches nothing and leaves every
+ * output untouched. */
 int tpsf_forward(const float* depth, const float* alpha_beta, float* HR, float* LR_deg, float* psf,
                  int B, void* stream);
 /* d loss / d (alpha, beta, gamma) (B,3) given d loss / d LR_deg (B,16); plateau pixels carry no
  * gradient, depth carries none (autograd of :118-125 as used by train/tPSFNet_train.py:180-190).  HR = the forward
  * output of the same (depth, alpha_beta) (tpsf_forward: the reductions over it are not recomputed); work: B*100*100
- * floats of scratch (the per-pixel dL/dHR between the two kernels). */
+ * floats of scratch (the per-pixel dL/dHR between the two kernels; exactly 0 on the plateau).  An all-plateau image has
+ * exactly zero gradients in all three components.
+ * Refusals: a NULL depth, alpha_beta, HR, dLR_deg, d_alpha_beta or work, or B <= 0, returns status 1, launches nothing and
+ * leaves d_alpha_beta and work untouched. */
 int tpsf_backward(const float* depth, const float* alpha_beta, const float* HR, const float* dLR_deg,
                   float* d_alpha_beta, float* work, int B, void* stream);
 /* C[i][j] = act(sum_k A(i,k)B(k,j) + bias[j]), A(i,k)=A[i*sa0+k*sa1], B(k,j)=B[k*sb0+j*sb1]; act 0 none,
- * 1 ReLU, 2 Softplus: the nn.Linear layers of MLP_layer (:26-36) and their backward GEMMs. */
+ * 1 ReLU, 2 Softplus: the nn.Linear layers of MLP_layer (:26-36) and their backward GEMMs.
+ * Refusals (the whole family: tsr_sgemm, tsr_sgemm_masked, tsr_sgemm_splitk, tsr_sgemm_splitk_strided, tsr_colsum_splitk): a
+ * NULL A, B or C / slab / Y (bias may be NULL; mask_ref may not), M, N or K <= 0, act outside 0..2, nsplit outside 1..65535,
+ * or a split_stride below the size of one partial (M*N; N for the column sums) returns status 1, launches nothing and leaves
+ * the output untouched. */
 int tsr_sgemm(const float* A, long long sa0, long long sa1, const float* B, long long sb0, long long sb1,
               const float* bias, float* C, int M, int N, int K, int act, void* stream);
 /* Split-K form for the reductions over the batch (dW = dy^T x, db = 1^T dy of the same layers): slab[s][M][N]
- * receives the partial product of K range s (no bias / activation); add the slabs with tsr_reduce_splits. */
+ * receives the partial product of K range s (no bias / activation); add the slabs with tsr_reduce_splits.
+ * Range s covers K indices [s*c, min((s+1)*c, K)) with c = ceil(K / nsplit) rounded up to whole 32-deep K steps.  Any nsplit in
+ * 1..65535 is valid: a split whose range is empty (nsplit above the number of K steps) still WRITES its partial, as exact
+ * zeros, so tsr_reduce_splits over all nsplit partials is always right and a slab needs no clearing.  The same holds for
+ * tsr_sgemm_splitk_strided and, with K = M rows, for tsr_colsum_splitk; neither touches the gap between partials. */
 int tsr_sgemm_splitk(const float* A, long long sa0, long long sa1, const float* B, long long sb0, long long sb1,
                      float* slab, int M, int N, int K, int nsplit, void* stream);
 /* dx GEMM of a layer with the ReLU backward of the layer below fused: C[i][j] = (sum_k A(i,k)B(k,j)) if mask_ref[i][j] > 0
