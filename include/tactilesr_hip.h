@@ -399,6 +399,14 @@ int tsr_stem_dgrad(const float* w_oihw, const float* dz, int dz_ctot, int dz_cof
 int tsr_head_bwd(const float* dout, const float* out, const float* h0, int h_ctot, int cin,
                  const float* w_oihw, float* dz_h0, int dz_ctot, float* wslab, int nsplit,
                  int B, int H, int W, float* dz_amax /* optional: max|dz_h0| */, void* stream);
+/* The activation-gradient half of tsr_head_bwd alone, for a train step whose 128 -> 1 head conv (reference
+ * model/tactileSR_model.py:55-56: Conv2d(128, 1, 3, padding=1, bias=False) + ReLU) is frozen while layers below it still
+ * train: dz_h0 = dgrad(dout*[out>0]) * [h0>0] and dz_amax are tsr_head_bwd's bit for bit (the same kernel launch), no weight
+ * partials are formed.  tsr_head_bwd's argument checks without the wslab / nsplit ones and without the (H + 2)(W + 2) bound,
+ * which is the weight gradient's; H * W <= 2^28. */
+int tsr_head_dgrad(const float* dout, const float* out, const float* h0, int h_ctot, int cin,
+                   const float* w_oihw, float* dz_h0, int dz_ctot, int B, int H, int W,
+                   float* dz_amax /* optional: max|dz_h0| */, void* stream);
 
 /* The same four kernels on bf16 CB16 tensors -- the train step with bf16 ACTIVATION STORAGE (tsr_conv_desc.nsplit = -1,
  * tsr_conv2d_wgrad_bf16s planes = -1): every stored activation / gradient tensor is bf16, arithmetic and the
@@ -422,6 +430,9 @@ int tsr_stem_wgrad_b16(const float* lr, int lr_ctot, int lr_coff, int hin, int w
 int tsr_head_bwd_b16(const float* dout, const float* out, const void* h0, int h_ctot, int cin,
                      const float* w_oihw, void* dz_h0, int dz_ctot, float* wslab, int nsplit,
                      int B, int H, int W, void* stream);
+/* tsr_head_dgrad on bf16 CB16 h0 / dz_h0 (reference model/tactileSR_model.py:55-56). */
+int tsr_head_dgrad_b16(const float* dout, const float* out, const void* h0, int h_ctot, int cin,
+                       const float* w_oihw, void* dz_h0, int dz_ctot, int B, int H, int W, void* stream);
 
 /* HR.float()/HR_scale_num + F.interpolate(size=(H,W), bilinear) (train/tactileSR_train.py:44-45). */
 int tsr_target_prep(const float* hr_raw, float* out, float inv_scale, int B, int hin, int win, int H, int W,

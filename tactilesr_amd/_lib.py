@@ -70,6 +70,7 @@ SIGNATURES = {
     "tsr_stem_wgrad": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
     "tsr_stem_dgrad": [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P],
     "tsr_head_bwd": [_P, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P],
+    "tsr_head_dgrad": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P],
     "tsr_cb16_stats_b16": [_P, _I, _I, _I, _I, _P, _P, _P],
     "tsr_bn_bwd_apply_b16": [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P],
     "tsr_bn_relu_b16": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P],
@@ -78,6 +79,7 @@ SIGNATURES = {
     "tsr_stem_wgrad_b16": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
     "tsr_stem_dgrad_b16": [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P],
     "tsr_head_bwd_b16": [_P, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P],
+    "tsr_head_dgrad_b16": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P],
     "tsr_target_prep": [_P, _P, _F, _I, _I, _I, _I, _I, _P],
     "tsr_mse_fwd_bwd": [_P, _P, _P, _P, _L, _F, _P, _P],
     "tsr_adam_l2_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P],

@@ -697,6 +697,33 @@ extern "C" int tsr_head_bwd_b16(const float* dout, const float* out, const void*
                              W, nullptr, stream);
 }
 
+// The activation-gradient half of tsr_head_bwd alone (a frozen output_layer.2.weight whose dz_h0 is still consumed): the same
+// head_bwd_kernel launch, so dz_h0 / dz_amax carry tsr_head_bwd's bits.  No LDS bound: that one is head_wgrad_kernel's.
+template <bool B16>
+static int head_dgrad_impl(const float* dout, const float* out, const float* h0, int h_ctot, int cin, const float* w_oihw,
+                           float* dz_h0, int dz_ctot, int B, int H, int W, float* dz_amax, void* stream) {
+  if (!dout || !out || !h0 || !w_oihw || !dz_h0 || (cin & 15) || cin > 256 || cin > h_ctot || cin > dz_ctot ||
+      (h_ctot & 15) || (dz_ctot & 15) || B <= 0 || H <= 0 || W <= 0)
+    return TSR_ERR_ARG;
+  if ((long long)H * W > (1 << 28)) return TSR_ERR_ARG;      // the kernel's (pixel, channel quad) item index is an int
+  const int items = H * W * 4;
+  hipLaunchKernelGGL(head_bwd_kernel<B16>, dim3((items + 255) / 256, B), dim3(256), (size_t)9 * cin * 4, (hipStream_t)stream,
+                     dout, out, h0, h_ctot, cin, w_oihw, dz_h0, dz_ctot, B, H, W, dz_amax);
+  return tsr_check_launch();
+}
+
+extern "C" int tsr_head_dgrad(const float* dout, const float* out, const float* h0, int h_ctot, int cin,
+                              const float* w_oihw, float* dz_h0, int dz_ctot, int B, int H, int W, float* dz_amax,
+                              void* stream) {
+  return head_dgrad_impl<false>(dout, out, h0, h_ctot, cin, w_oihw, dz_h0, dz_ctot, B, H, W, dz_amax, stream);
+}
+
+extern "C" int tsr_head_dgrad_b16(const float* dout, const float* out, const void* h0, int h_ctot, int cin,
+                                  const float* w_oihw, void* dz_h0, int dz_ctot, int B, int H, int W, void* stream) {
+  return head_dgrad_impl<true>(dout, out, (const float*)h0, h_ctot, cin, w_oihw, (float*)dz_h0, dz_ctot, B, H, W, nullptr,
+                               stream);
+}
+
 // ------------------------------------------------------------------------------------------
 // target preparation: HR_raw (B,1,hin,win) * inv_scale -> bilinear (align_corners=False) to (H,W)
 // (train/tactileSR_train.py:44-45: HR/HR_scale_num, F.interpolate(size=(4sf,4sf)))

@@ -125,8 +125,12 @@ class GradSink:
     """What a backward engine writes its parameter gradients through (one per backward call).
 
     ``owner`` is the engine: it carries ``arena`` (None until the first backward has revealed the production order),
-    ``grad_sync`` (None on one GPU) and ``n_buckets``.  Three cases:
-      direct  -- the arena exists and every parameter's .grad is None (``zero_grad()``'s default): ``dest`` hands out
+    ``grad_sync`` (None on one GPU) and ``n_buckets``.  ``want`` (optional) names the parameters this backward produces
+    a gradient for -- the trainable ones; frozen parameters have no arena slot, and a stale ``.grad`` one of them still
+    carries does not count below.  An arena laid out for another want-set is dropped like one laid out for another
+    module tree: this backward takes the ``first`` path again (the GradSync is re-bound, the fused Adam builds one new
+    chunk table).  Without ``want`` every parameter of ``named_params`` counts.  The cases:
+      direct  -- the arena exists and every wanted parameter's .grad is None (``zero_grad()``'s default): ``dest`` hands out
                  arena views, ``put`` ticks the arena, complete buckets go to the wire from inside backward;
       first   -- no arena yet: gradients land in fresh tensors while the order is recorded; ``finalize`` builds the
                  arena in that order, moves them in and binds the GradSync (buckets are reduced in ``finish``);
@@ -141,12 +145,15 @@ class GradSink:
                  ``.grad`` tensors.
     """
 
-    def __init__(self, owner, named_params: Dict[str, torch.nn.Parameter], device, token=None):
+    def __init__(self, owner, named_params: Dict[str, torch.nn.Parameter], device, token=None, want=None):
         self.owner, self.device = owner, device
         arena = getattr(owner, "arena", None)
         if arena is not None and any(n not in named_params or named_params[n].shape != arena.shapes[n]
                                      for n in arena.names):
             arena = owner.arena = None                                   # the module tree changed: lay out again
+        if arena is not None and want and set(arena.names) != set(want):
+            arena = owner.arena = None                                   # another set of parameters trains: lay out again
+        counted = named_params.values() if want is None else [named_params[n] for n in want if n in named_params]
         live = getattr(owner, "_live_forwards", None)
         alone = True
         if live is not None:
@@ -157,7 +164,7 @@ class GradSink:
         owner._shared_graph = self.shared and not alone                  # the graph's last backward clears the mark
         self.first = arena is None and not self.shared
         self.direct = (arena is not None and not self.shared
-                       and all(p.grad is None for p in named_params.values()))
+                       and all(p.grad is None for p in counted))
         self.arena = arena if self.direct else None
         sync = getattr(owner, "grad_sync", None)
         if sync is not None:
@@ -187,7 +194,7 @@ class GradSink:
         self.put(name, d)
 
     def finalize(self) -> Dict[str, torch.Tensor]:
-        if self.first:
+        if self.first and self.order:
             arena = GradArena(self.order, self.device, getattr(self.owner, "n_buckets", 8))
             for n, t in self.out.items():
                 arena.view(n).copy_(t)
@@ -237,9 +244,44 @@ class GradSync:
 
     # ---- wiring ----------------------------------------------------------------------------------------------
     def bind(self, arena: GradArena) -> None:
-        """Called by the backward engine once its arena exists (after the first backward)."""
+        """Called by the backward engine once its arena exists (after the first backward, and again whenever the set
+        of trainable parameters changed and the arena was laid out anew).  With more than one rank the layouts are
+        compared first: ranks that froze different parameters would reduce different tensors into each other."""
+        self._check_layout(arena)
         self.arena = arena
         arena.on_bucket_ready = self._bucket_ready
+
+    _LAYOUT_SLOTS = 256
+
+    def _check_layout(self, arena: GradArena) -> None:
+        """One small all-gather of a fixed-size table of running 63-bit hashes over the arena's (name, offset) pairs --
+        entry i covers the first i + 1 pairs, the last entry the whole layout -- so the first entry that differs
+        between two ranks points at the first parameter whose slot differs."""
+        ranks = dist.get_world_size(self.group) if dist.is_initialized() else 1      # (the group's own size: it is a collective)
+        if self.world == 1 or ranks < 2:
+            return
+        import hashlib
+        h = hashlib.blake2b(digest_size=8)
+        table = []
+        for n in arena.names:
+            h.update(f"{n}@{arena.offsets[n]};".encode())
+            table.append(int.from_bytes(h.digest(), "little") >> 1)
+        h.update(f"total@{arena.total}".encode())
+        whole = int.from_bytes(h.digest(), "little") >> 1
+        k = self._LAYOUT_SLOTS
+        table = (table[:k - 1] + [whole] * k)[:k - 1] + [whole]
+        mine = torch.tensor(table, dtype=torch.int64, device=arena.flat.device)
+        every = [torch.empty_like(mine) for _ in range(ranks)]
+        dist.all_gather(every, mine, group=self.group)
+        for r, other in enumerate(every):
+            diff = (other != mine).nonzero()
+            if diff.numel():
+                i = int(diff[0])
+                here = arena.names[i] if i < min(len(arena.names), k - 1) else "<end of the layout>"
+                raise RuntimeError(
+                    f"GradSync: the gradient arena of this rank differs from rank {r}'s from entry {i} on ('{here}' "
+                    f"here): every rank must train (and freeze) the same parameters -- a mismatch would reduce "
+                    f"different tensors into each other")
 
     def no_sync(self):
         """Context manager: backward passes inside it put nothing on the wire (micro-batches of an accumulated step)."""

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes
 from ctypes import c_int, c_void_p, c_float, c_double, c_longlong, POINTER, byref
+from typing import NamedTuple
 
 import torch
 
@@ -34,6 +35,125 @@ def check_trainable_size(H, W):
         raise _lib.TactileSRHipError(
             f"train step at {H}x{W} output: tsr_head_bwd needs (H+2)*(W+2)*4 <= {HEAD_BWD_LDS_BYTES} bytes of LDS "
             f"(at most 126x126, scale_factor <= 31 on 4x4 taxels)")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Backward plan (host only: no device, no library).  One record per launch of TrainEngine.backward / BlockEngine.backward in
+# the order the engines issue them.  Labels name gradient tensors; a "saved:" label is a tensor the forward kept (or the
+# incoming dout) and has no producer.  The BatchNorm sums a dgrad(bn=True) epilogue leaves in the statistics slab are an
+# output of that dgrad (label "<tensor>.sums"), consumed by the bn_bwd_finalize behind it; the coefficients a finalize
+# writes ("<bn>.coef") are consumed by its bn_bwd_apply, which turns the masked gradient g into dz in place.
+# ---------------------------------------------------------------------------------------------------------------------
+class Record(NamedTuple):
+    kind: str           # head_bwd | head_dgrad | wgrad | dgrad | bn_bwd_finalize | bn_bwd_apply | stem_wgrad | stem_dgrad
+    layer: str          # module path of the conv / BatchNorm (+ "[a:b]" for a dgrad over an input-channel slice)
+    consumes: tuple     # gradient-tensor labels read
+    produces: tuple     # gradient-tensor labels written
+    params: tuple       # parameter-gradient names the launch (and its tsr_reduce_splits) produces
+
+    @property
+    def key(self):
+        return self.kind, self.layer
+
+
+def _res_records(p, dpre):
+    """Launches of `_res_bwd` for the ResBlock with parameter prefix `p` ("" or "path."); `dpre` labels its incoming gradient."""
+    d1, dx = p + "d1", p + "dx"
+    return [
+        Record("wgrad", p + "conv2", (dpre,), (), (p + "conv2.weight", p + "conv2.bias")),
+        Record("dgrad", p + "conv2", (dpre,), (d1,), ()),
+        Record("wgrad", p + "conv1", (d1,), (), (p + "conv1.weight", p + "conv1.bias")),
+        Record("dgrad", p + "conv1", (d1, dpre), (dx,), ()),
+    ]
+
+
+def _msrb_records(p, dpre, virtual):
+    """Launches of `_msrb_bwd` for the MSRB with parameter prefix `p`; `virtual`: the block input is relu(bn(z)) of the layer
+    below, so the last dgrad's epilogue also leaves that BatchNorm's backward sums."""
+    recs = [Record("wgrad", p + "confusion", (dpre,), (), (p + "confusion.weight", p + "confusion.bias"))]
+    for o, nm in ((0, "conv_3_2"), (128, "conv_5_2")):
+        sl = f"[{o}:{o + 128}]"
+        g, dz, bn = p + "g2" + sl, p + "dz2" + sl, p + nm + ".1"
+        recs += [Record("dgrad", p + "confusion" + sl, (dpre,), (g, g + ".sums"), ()),
+                 Record("bn_bwd_finalize", bn, (g + ".sums",), (bn + ".coef",), (bn + ".weight", bn + ".bias")),
+                 Record("bn_bwd_apply", bn, (g, bn + ".coef"), (dz,), ())]
+    dz32, dz52 = p + "dz2[0:128]", p + "dz2[128:256]"
+    bn1 = p + "conv_3_1.1|conv_5_1.1"
+    recs += [
+        Record("wgrad", p + "conv_3_2.0", (dz32,), (), (p + "conv_3_2.0.weight", p + "conv_3_2.0.bias")),
+        Record("wgrad", p + "conv_5_2.0", (dz52,), (), (p + "conv_5_2.0.weight", p + "conv_5_2.0.bias")),
+        Record("dgrad", p + "conv_3_2.0", (dz32,), (p + "g1.3",), ()),
+        Record("dgrad", p + "conv_5_2.0", (dz52, p + "g1.3"), (p + "g1", p + "g1.sums"), ()),
+        Record("bn_bwd_finalize", bn1, (p + "g1.sums",), (bn1 + ".coef",),
+               (p + "conv_3_1.1.weight", p + "conv_3_1.1.bias", p + "conv_5_1.1.weight", p + "conv_5_1.1.bias")),
+        Record("bn_bwd_apply", bn1, (p + "g1", bn1 + ".coef"), (p + "dz1",), ()),
+        Record("wgrad", p + "conv_3_1.0", (p + "dz1",), (), (p + "conv_3_1.0.weight", p + "conv_3_1.0.bias")),
+        Record("wgrad", p + "conv_5_1.0", (p + "dz1",), (), (p + "conv_5_1.0.weight", p + "conv_5_1.0.bias")),
+        Record("dgrad", p + "conv_3_1.0", (p + "dz1", dpre), (p + "dx.3",), ()),
+        Record("dgrad", p + "conv_5_1.0", (p + "dz1", p + "dx.3"), (p + "dx",) + ((p + "dx.sums",) if virtual else ()), ()),
+    ]
+    return recs
+
+
+def _prune(recs, want, want_out):
+    """The records that something wanting a gradient depends on: one of its parameter gradients is in `want`, or one of its
+    outputs is in `want_out` or is consumed by a kept record (one sweep from the back: consumers follow producers).  A kept
+    head_bwd whose weight gradient nobody wants becomes head_dgrad (tsr_head_dgrad: the same dz_h0, no weight partials)."""
+    need, keep = set(want_out), []
+    for r in reversed(recs):
+        if any(n in want for n in r.params) or any(t in need for t in r.produces):
+            need.update(r.consumes)
+            if r.kind == "head_bwd" and not any(n in want for n in r.params):
+                r = Record("head_dgrad", r.layer, r.consumes, r.produces, ())
+            keep.append(r)
+    keep.reverse()
+    return keep
+
+
+def backward_plan(seqsCnt, n_msrb, n_res, want, want_dx=False):
+    """Launch list of `TrainEngine.backward` for a TactileSR of `seqsCnt` frames, `n_msrb` MSRBs and `n_res` ResBlocks when
+    the parameter gradients named in `want` (and, with `want_dx`, the taxel gradient "LR.grad") are asked for.  `want` = every
+    parameter name gives the unfiltered list: the all-trainable step."""
+    recs = [Record("head_bwd", "output_layer.2", ("saved:dout",), ("dz_h0",), ("output_layer.2.weight",)),
+            Record("wgrad", "output_layer.0", ("dz_h0",), (), ("output_layer.0.weight",)),
+            Record("dgrad", "output_layer.0", ("dz_h0",), ("g_hcat[0:64]", "g_hcat[64:128]"), ())]
+    dpre = "g_hcat[0:64]"
+    for i in reversed(range(n_res)):
+        p = f"forceFeatureExtra_layer.{i}."
+        recs += _res_records(p, dpre)
+        dpre = p + "dx"
+    recs += [Record("stem_wgrad", "input_layer_force.1", (dpre,), (), ("input_layer_force.1.weight",)),
+             Record("stem_dgrad", "input_layer_force.1", (dpre,), ("LR.grad",), ())]
+    dpre = "g_hcat[64:128]"
+    for i in reversed(range(n_msrb)):
+        p = f"patternFeatureExtra_layer.{i}."
+        recs += _msrb_records(p, dpre, virtual=(i == 0))
+        dpre = p + "dx"
+    bn = "inputContact_layer.1"
+    recs += [Record("bn_bwd_finalize", bn, (dpre + ".sums",), (bn + ".coef",), (bn + ".weight", bn + ".bias")),
+             Record("bn_bwd_apply", bn, (dpre, bn + ".coef"), ("dzf",), ()),
+             Record("wgrad", "inputContact_layer.0", ("dzf",), (), ("inputContact_layer.0.weight",))]
+    for t in range(seqsCnt):
+        p = f"inputLayer_pattern_list.{t}."
+        sl = f"[{64 * t}:{64 * t + 64}]"
+        gT, dzT = "gT" + sl, "dzT" + sl
+        recs += [Record("dgrad", "inputContact_layer.0" + sl, ("dzf",), (gT, gT + ".sums"), ()),
+                 Record("bn_bwd_finalize", p + "5", (gT + ".sums",), (p + "5.coef",), (p + "5.weight", p + "5.bias")),
+                 Record("bn_bwd_apply", p + "5", (gT, p + "5.coef"), (dzT,), ()),
+                 Record("wgrad", p + "4", (dzT,), (), (p + "4.weight",)),
+                 Record("dgrad", p + "4", (dzT,), (p + "g1", p + "g1.sums"), ()),
+                 Record("bn_bwd_finalize", p + "2", (p + "g1.sums",), (p + "2.coef",), (p + "2.weight", p + "2.bias")),
+                 Record("bn_bwd_apply", p + "2", (p + "g1", p + "2.coef"), (p + "dz1",), ()),
+                 Record("stem_wgrad", p + "1", (p + "dz1",), (), (p + "1.weight",)),
+                 Record("stem_dgrad", p + "1", (p + "dz1",), ("LR.grad",), ())]
+    return _prune(recs, frozenset(want), ("LR.grad",) if want_dx else ())
+
+
+def block_backward_plan(kind, want, want_dx=True):
+    """`backward_plan` for a standalone ``MSRB`` (`kind` "msrb") / ``ResBlock`` ("res"): parameter names carry no prefix, the
+    incoming gradient is "saved:dpre" and "dx" is the gradient of the block input."""
+    recs = _msrb_records("", "saved:dpre", virtual=False) if kind == "msrb" else _res_records("", "saved:dpre")
+    return _prune(recs, frozenset(want), ("dx",) if want_dx else ())
 
 
 class ConvDesc(ctypes.Structure):
@@ -392,6 +512,7 @@ class TrainEngine:
         c = self._new_ctx(B, H, W, dev)
         c.x, c.hin, c.win = x.detach(), hin, win
         c.want_dx = False        # TactileSRTrainFn sets it when the taxels require grad: backward then also returns dx
+        c.want = self._want_default(m.named_parameters())      # (TactileSRTrainFn: what autograd asks for instead)
         st_entries = c.st_entries
 
         def buf(ch):
@@ -526,6 +647,10 @@ class TrainEngine:
         return max(1, min(B * tiles, (1024 if self.nsplit else 1536) // slices))   # 2 (16-bit) / 3 (f32) WGs per CU
 
     def _wgrad(self, c, a: Act, dz: Act, conv, grads, name, with_bias):
+        """The weight-gradient launch of `conv` (plan record ("wgrad", name)): it runs whole when its weight or its bias
+        gradient is wanted; only the wanted ones are reduced out of the split slabs and handed to `grads`."""
+        if ("wgrad", name) not in c.live:
+            return
         w = conv.weight
         cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
         if self.io16 and _lib.load().tsr_conv2d_wgrad_b16k(cout, cin, ks):
@@ -546,10 +671,11 @@ class TrainEngine:
                 call("tsr_conv2d_wgrad", ptr(a.buf), _I(a.ctot), _I(a.coff), _I(cin), ptr(a.scale), ptr(a.shift),
                      ptr(dz.buf), _I(dz.ctot), _I(dz.coff), _I(cout), _I(ks), ptr(slab), ptr(bslab), _I(ns),
                      _I(c.B), _I(c.H), _I(c.W), stream())
-        gw = grads.dest(name + ".weight", w.shape)
-        call("tsr_reduce_splits", ptr(slab), ptr(gw), _L(n), _I(ns), _F(1.0), stream())
-        grads.put(name + ".weight", gw)
-        if with_bias:
+        if name + ".weight" in c.want:
+            gw = grads.dest(name + ".weight", w.shape)
+            call("tsr_reduce_splits", ptr(slab), ptr(gw), _L(n), _I(ns), _F(1.0), stream())
+            grads.put(name + ".weight", gw)
+        if with_bias and name + ".bias" in c.want:
             gb = grads.dest(name + ".bias", (cout,))
             call("tsr_reduce_splits", ptr(bslab), ptr(gb), _L(cout), _I(ns), _F(1.0), stream())
             grads.put(name + ".bias", gb)
@@ -573,19 +699,29 @@ class TrainEngine:
                     out_amax=out_amax)
         c.last_entries = self._entries(c, nprime, ks, ns)      # what a following _bn_bwd reduces
 
-    def _bn_bwd(self, c, g_buf, g_ctot, g_coff, z: Act, zoff, C, bn_vec, bn_mod, grads, name, out_amax=None, gnames=None):
+    def _bn_bwd(self, c, layer, g_buf, g_ctot, g_coff, z: Act, zoff, C, bn_vec, bn_mod, grads, name, out_amax=None,
+                gnames=None):
         """Finish BatchNorm backward for C channels whose masked gradient g sits in g_buf (slab sums
         were just produced by the dgrad epilogue over the same C channels).  `gnames` = (weight, bias) parameter names:
-        dgamma / dbeta are then written straight into their gradient slots (no copy launches)."""
+        the wanted ones of dgamma / dbeta are then written straight into their gradient slots (no copy launches).
+        Plan records ("bn_bwd_finalize", layer) -- needed for dgamma / dbeta or for the apply pass -- and
+        ("bn_bwd_apply", layer), which turns g into dz in place and runs only when dz is consumed."""
+        if ("bn_bwd_finalize", layer) not in c.live:
+            return None
         dev = g_buf.device
         out = torch.empty(5, C, dtype=torch.float32, device=dev)
-        dg, db = (grads.dest(gnames[0], (C,)), grads.dest(gnames[1], (C,))) if gnames else (out[0], out[1])
+        gnames = tuple(n if n in c.want else None for n in gnames) if gnames else (None, None)
+        dg = grads.dest(gnames[0], (C,)) if gnames[0] else out[0]
+        db = grads.dest(gnames[1], (C,)) if gnames[1] else out[1]
         call("tsr_bn_bwd_finalize", ptr(c.slab), _I(c.last_entries), _I(C), _D(float(c.B * c.HW)),
              ptr(bn_vec[0]), ptr(bn_vec[2]), ptr(bn_vec[3]), ptr(dg), ptr(db), ptr(out[2]), ptr(out[3]),
              ptr(out[4]), ptr(c.work), stream())
-        if gnames:
+        if gnames[0]:
             grads.put(gnames[0], dg)
+        if gnames[1]:
             grads.put(gnames[1], db)
+        if ("bn_bwd_apply", layer) not in c.live:
+            return out
         if self.io16:
             call("tsr_bn_bwd_apply_b16", ptr(g_buf), _I(g_ctot), _I(g_coff), ptr(z.buf), _I(z.ctot), _I(z.coff + zoff),
                  ptr(out[2]), ptr(out[3]), ptr(out[4]), _I(C), _I(c.B), _I(c.HW), stream())
@@ -596,15 +732,20 @@ class TrainEngine:
 
     def _res_bwd(self, c, s, rb, name, dpre: Act, grads, new_amax, buf, mask_input=True):
         """Backward of one ResBlock.  `dpre` = gradient w.r.t. the block output BEFORE its ReLU; returns the gradient
-        w.r.t. the block input -- masked by the input's own ReLU pattern (`mask_input`, the chained engine: the input is
-        the previous block's post-ReLU output) or plain (standalone module)."""
+        w.r.t. the block input (None when the backward plan has no launch producing it) -- masked by the input's own ReLU
+        pattern (`mask_input`, the chained engine: the input is the previous block's post-ReLU output) or plain (standalone
+        module)."""
         name = name + "." if name else ""          # (standalone module: parameter names carry no prefix)
         F1 = s.F1
         self._wgrad(c, F1, dpre, rb.conv2, grads, name + "conv2", True)
+        if ("dgrad", name + "conv2") not in c.live:      # nothing below conv2 wants a gradient
+            return None
         d1 = buf(64)
         D1 = Act(d1, 64, 0, 64, amax=new_amax())
         self._dgrad(c, dpre, rb.conv2, 0, 64, d1, 64, 0, mask=F1, out_amax=D1.amax)
         self._wgrad(c, s.X, D1, rb.conv1, grads, name + "conv1", True)
+        if ("dgrad", name + "conv1") not in c.live:
+            return None
         d0 = buf(64)
         am = new_amax()
         self._dgrad(c, D1, rb.conv1, 0, 64, d0, 64, 0, res=dpre, mask=s.X if mask_input else None, out_amax=am)
@@ -612,42 +753,52 @@ class TrainEngine:
 
     def _msrb_bwd(self, c, s, blk, name, dpre: Act, grads, new_amax, buf, tag="msrb", mask_input=True):
         """Backward of one MSRB.  `dpre` = gradient w.r.t. the block output BEFORE its ReLU; returns the gradient w.r.t.
-        the block input: masked by the input's ReLU pattern / with the BatchNorm-backward sums of a virtual input
-        (`mask_input`, the chained engine) or plain (standalone module)."""
+        the block input (None when the backward plan has no launch producing it): masked by the input's ReLU pattern / with
+        the BatchNorm-backward sums of a virtual input (`mask_input`, the chained engine) or plain (standalone module)."""
         name = name + "." if name else ""          # (standalone module: parameter names carry no prefix)
+        on = lambda kind, layer: (kind, name + layer) in c.live
         # confusion 1x1: a = relu(bn(cat2)), dz = dpre
         self._wgrad(c, s.A2, dpre, blk.confusion, grads, name + "confusion", True)
+        if not (on("dgrad", "confusion[0:128]") or on("dgrad", "confusion[128:256]")):
+            return None
         g2 = buf(256)
         am_g2 = [new_amax(), new_amax()]
         for half, (cv, bnm, nm) in enumerate(((blk.conv_3_2[0], blk.conv_3_2[1], "conv_3_2"),
                                               (blk.conv_5_2[0], blk.conv_5_2[1], "conv_5_2"))):
             o = 128 * half
+            if not on("dgrad", f"confusion[{o}:{o + 128}]"):
+                continue
             mk = Act(s.cat2, 256, o, 128, s.bn_c2[0, o:o + 128], s.bn_c2[1, o:o + 128], s.bn_c2[2, o:o + 128],
                      s.bn_c2[3, o:o + 128])
             self._dgrad(c, dpre, blk.confusion, o, 128, g2, 256, o, mask=mk, bn=True)
-            self._bn_bwd(c, g2, 256, o, Act(s.cat2, 256, 0, 256), o, 128, s.bn_c2[:, o:o + 128], bnm, grads,
+            self._bn_bwd(c, f"{name}{nm}.1", g2, 256, o, Act(s.cat2, 256, 0, 256), o, 128, s.bn_c2[:, o:o + 128], bnm, grads,
                          nm, out_amax=am_g2[half], gnames=(f"{name}{nm}.1.weight", f"{name}{nm}.1.bias"))
         if self.debug is not None:
             self.debug[f"{tag}.dz2"] = g2.clone()
         DZ32, DZ52 = Act(g2, 256, 0, 128, amax=am_g2[0]), Act(g2, 256, 128, 128, amax=am_g2[1])
         self._wgrad(c, s.A1, DZ32, blk.conv_3_2[0], grads, f"{name}conv_3_2.0", True)
         self._wgrad(c, s.A1, DZ52, blk.conv_5_2[0], grads, f"{name}conv_5_2.0", True)
+        if not on("dgrad", "conv_5_2.0"):          # (the two stage-2 dgrads fill one tensor: both are planned or neither)
+            return None
         g1 = buf(128)
         self._dgrad(c, DZ32, blk.conv_3_2[0], 0, 128, g1, 128, 0)
         mk = Act(s.cat1, 128, 0, 128, s.bn_c1[0], s.bn_c1[1], s.bn_c1[2], s.bn_c1[3])
         self._dgrad(c, DZ52, blk.conv_5_2[0], 0, 128, g1, 128, 0, res=Act(g1, 128, 0, 128), mask=mk, bn=True)
         am_g1 = new_amax()
-        r = self._bn_bwd(c, g1, 128, 0, Act(s.cat1, 128, 0, 128), 0, 128, s.bn_c1, None, grads, "", out_amax=am_g1)
-        grads.put_copy(f"{name}conv_3_1.1.weight", r[0, :64])
-        grads.put_copy(f"{name}conv_3_1.1.bias", r[1, :64])
-        grads.put_copy(f"{name}conv_5_1.1.weight", r[0, 64:])
-        grads.put_copy(f"{name}conv_5_1.1.bias", r[1, 64:])
+        r = self._bn_bwd(c, f"{name}conv_3_1.1|conv_5_1.1", g1, 128, 0, Act(s.cat1, 128, 0, 128), 0, 128, s.bn_c1, None,
+                         grads, "", out_amax=am_g1)
+        for gname, row in ((f"{name}conv_3_1.1.weight", r[0, :64]), (f"{name}conv_3_1.1.bias", r[1, :64]),
+                           (f"{name}conv_5_1.1.weight", r[0, 64:]), (f"{name}conv_5_1.1.bias", r[1, 64:])):
+            if gname in c.want:
+                grads.put_copy(gname, row)
         del g2
         if self.debug is not None:
             self.debug[f"{tag}.dz1"] = g1.clone()
         DZ31, DZ51 = Act(g1, 128, 0, 64, amax=am_g1), Act(g1, 128, 64, 64, amax=am_g1)
         self._wgrad(c, s.X, DZ31, blk.conv_3_1[0], grads, f"{name}conv_3_1.0", True)
         self._wgrad(c, s.X, DZ51, blk.conv_5_1[0], grads, f"{name}conv_5_1.0", True)
+        if not on("dgrad", "conv_5_1.0"):          # (likewise one tensor: dx)
+            return None
         dx = buf(64)
         self._dgrad(c, DZ31, blk.conv_3_1[0], 0, 64, dx, 64, 0, res=dpre)
         virtual = mask_input and s.X.scale is not None
@@ -657,12 +808,20 @@ class TrainEngine:
         return Act(dx, 64, 0, 64, amax=am)
 
     # ------------------------------------------------------------------ backward
+    def _want_default(self, named):
+        """The want-set of a forward that autograd did not record (the engine driven directly): `requires_grad`."""
+        return frozenset(n for n, p in named if p.requires_grad)
+
     def backward(self, c: _Ctx, dout: torch.Tensor):
         m = self.m
         dev = dout.device
         B, H, W, HW = c.B, c.H, c.W, c.HW
         from ..ddp import GradSink
-        grads = GradSink(self, dict(m.named_parameters()), dev, token=c)
+        T = m.seqsCnt
+        # the launches something that wants a gradient depends on (all of today's list when every parameter is trainable)
+        c.live = {r.key for r in backward_plan(T, len(c.blocks), len(c.res), c.want, c.want_dx)}
+        on = lambda kind, layer: (kind, layer) in c.live
+        grads = GradSink(self, dict(m.named_parameters()), dev, token=c, want=c.want)
 
         def buf(ch):
             return torch.empty(B * ch * HW, dtype=self.act_dtype, device=dev)
@@ -672,25 +831,36 @@ class TrainEngine:
         # taxel gradient (only when the input requires grad): frame 0 gets the force stem's store, then its pattern stem's add
         dx = torch.empty(c.x.shape, dtype=torch.float32, device=dev) if c.want_dx else None
         c.dx = dx
+        if not c.live:
+            return grads.finalize()
         # ---- head: out = relu(conv(h0)), h0 = relu(conv(hcat))
-        ns = max(1, min(B * (8 if H > 64 else 1), 2048))     # (image split, row band) entries: ~8 resident workgroups per CU
         dz_h0 = buf(128)
         am_dzh0 = new_amax()
-        wslab = torch.empty(ns * 128 * 9, dtype=torch.float32, device=dev)
-        if self.io16:
-            call("tsr_head_bwd_b16", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
-                 ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), ptr(wslab), _I(ns), _I(B), _I(H), _I(W),
-                 stream())
+        if on("head_bwd", "output_layer.2"):
+            ns = max(1, min(B * (8 if H > 64 else 1), 2048))     # (image split, row band) entries: ~8 resident workgroups per CU
+            wslab = torch.empty(ns * 128 * 9, dtype=torch.float32, device=dev)
+            if self.io16:
+                call("tsr_head_bwd_b16", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
+                     ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), ptr(wslab), _I(ns), _I(B), _I(H), _I(W),
+                     stream())
+            else:
+                call("tsr_head_bwd", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
+                     ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), ptr(wslab), _I(ns), _I(B), _I(H), _I(W),
+                     ptr(am_dzh0), stream())
+            gw = grads.dest("output_layer.2.weight", m.output_layer[2].weight.shape)
+            call("tsr_reduce_splits", ptr(wslab), ptr(gw), _L(128 * 9), _I(ns), _F(1.0), stream())
+            grads.put("output_layer.2.weight", gw)
+        elif self.io16:       # ("head_dgrad", "output_layer.2"): the head weight is frozen, dz_h0 is still consumed
+            call("tsr_head_dgrad_b16", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
+                 ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), _I(B), _I(H), _I(W), stream())
         else:
-            call("tsr_head_bwd", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
-                 ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), ptr(wslab), _I(ns), _I(B), _I(H), _I(W),
-                 ptr(am_dzh0), stream())
-        gw = grads.dest("output_layer.2.weight", m.output_layer[2].weight.shape)
-        call("tsr_reduce_splits", ptr(wslab), ptr(gw), _L(128 * 9), _I(ns), _F(1.0), stream())
-        grads.put("output_layer.2.weight", gw)
+            call("tsr_head_dgrad", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
+                 ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), _I(B), _I(H), _I(W), ptr(am_dzh0), stream())
         DZ = Act(dz_h0, 128, 0, 128, amax=am_dzh0)
         HC = Act(c.hcat, 128, 0, 128, amax=c.am_hcat)
         self._wgrad(c, HC, DZ, m.output_layer[0], grads, "output_layer.0", False)
+        if not on("dgrad", "output_layer.0"):          # only the head trains
+            return grads.finalize()
         g_hcat = buf(128)
         am_ghcat = new_amax()
         self._dgrad(c, DZ, m.output_layer[0], 0, 128, g_hcat, 128, 0, mask=HC, out_amax=am_ghcat)
@@ -702,55 +872,66 @@ class TrainEngine:
         # ---- force branch (ResBlocks, reversed); gradient w.r.t. block output pre-ReLU in `dpre`
         dpre = Act(g_hcat, 128, 0, 64, amax=am_ghcat)
         for i in reversed(range(len(c.res))):
-            dpre = self._res_bwd(c, c.res[i], m.forceFeatureExtra_layer[i], f"forceFeatureExtra_layer.{i}", dpre, grads,
-                                 new_amax, buf)
-        ns = max(1, min(B, 2048))     # image splits: ~8 resident workgroups per CU hide the load latency
-        sslab = torch.empty(ns * 64 * 27, dtype=torch.float32, device=dev)
-        call("tsr_stem_wgrad_b16" if self.io16 else "tsr_stem_wgrad", ptr(c.x), _I(c.x.shape[1]), _I(0), _I(c.hin),
-             _I(c.win), _I(m.scale_factor), ptr(dpre.buf), _I(dpre.ctot), _I(dpre.coff), ptr(sslab), _I(ns), _I(B), stream())
-        gw = grads.dest("input_layer_force.1.weight", m.input_layer_force[1].weight.shape)
-        call("tsr_reduce_splits", ptr(sslab), ptr(gw), _L(64 * 27), _I(ns), _F(1.0), stream())
-        grads.put("input_layer_force.1.weight", gw)
-        if dx is not None:
+            if dpre is not None:
+                dpre = self._res_bwd(c, c.res[i], m.forceFeatureExtra_layer[i], f"forceFeatureExtra_layer.{i}", dpre, grads,
+                                     new_amax, buf)
+        if on("stem_wgrad", "input_layer_force.1"):
+            ns = max(1, min(B, 2048))     # image splits: ~8 resident workgroups per CU hide the load latency
+            sslab = torch.empty(ns * 64 * 27, dtype=torch.float32, device=dev)
+            call("tsr_stem_wgrad_b16" if self.io16 else "tsr_stem_wgrad", ptr(c.x), _I(c.x.shape[1]), _I(0), _I(c.hin),
+                 _I(c.win), _I(m.scale_factor), ptr(dpre.buf), _I(dpre.ctot), _I(dpre.coff), ptr(sslab), _I(ns), _I(B),
+                 stream())
+            gw = grads.dest("input_layer_force.1.weight", m.input_layer_force[1].weight.shape)
+            call("tsr_reduce_splits", ptr(sslab), ptr(gw), _L(64 * 27), _I(ns), _F(1.0), stream())
+            grads.put("input_layer_force.1.weight", gw)
+        if on("stem_dgrad", "input_layer_force.1"):
             self._stem_dgrad(c, m.input_layer_force[1].weight, dpre.buf, dpre.ctot, dpre.coff, dx, 0, 0)
 
         # ---- pattern branch: MSRB blocks reversed
         dpre = Act(g_hcat, 128, 64, 64, amax=am_ghcat)
         for i in reversed(range(len(c.blocks))):
-            dpre = self._msrb_bwd(c, c.blocks[i], m.patternFeatureExtra_layer[i], f"patternFeatureExtra_layer.{i}", dpre,
-                                  grads, new_amax, buf, tag=f"msrb{i}")
+            if dpre is not None:
+                dpre = self._msrb_bwd(c, c.blocks[i], m.patternFeatureExtra_layer[i], f"patternFeatureExtra_layer.{i}", dpre,
+                                      grads, new_amax, buf, tag=f"msrb{i}")
+        if dpre is None:          # nothing at or below the first MSRB's input wants a gradient
+            return grads.finalize()
         # X of block 0 is the fuse conv's relu(bn(zf)): finish its BN backward -> dzf
-        self._bn_bwd(c, dpre.buf, 64, 0, Act(c.zf, 64, 0, 64), 0, 64, c.bnf, None, grads, "", out_amax=dpre.amax,
-                     gnames=("inputContact_layer.1.weight", "inputContact_layer.1.bias"))
-        T = m.seqsCnt
+        self._bn_bwd(c, "inputContact_layer.1", dpre.buf, 64, 0, Act(c.zf, 64, 0, 64), 0, 64, c.bnf, None, grads, "",
+                     out_amax=dpre.amax, gnames=("inputContact_layer.1.weight", "inputContact_layer.1.bias"))
         AT = Act(c.catT, 64 * T, 0, 64 * T, c.bn2[0], c.bn2[1], c.bn2[2], c.bn2[3], amax=c.am_catT)
         self._wgrad(c, AT, dpre, m.inputContact_layer[0], grads, "inputContact_layer.0", False)
         gT = buf(64 * T)
         for t, seq in enumerate(m.inputLayer_pattern_list):
             name = f"inputLayer_pattern_list.{t}"
             o = 64 * t
+            if not on("dgrad", f"inputContact_layer.0[{o}:{o + 64}]"):
+                continue
             mk = Act(c.catT, 64 * T, o, 64, c.bn2[0, o:o + 64], c.bn2[1, o:o + 64], c.bn2[2, o:o + 64],
                      c.bn2[3, o:o + 64])
             self._dgrad(c, dpre, m.inputContact_layer[0], o, 64, gT, 64 * T, o, mask=mk, bn=True)
             am_gT = new_amax()
-            self._bn_bwd(c, gT, 64 * T, o, Act(c.catT, 64 * T, 0, 64 * T), o, 64, c.bn2[:, o:o + 64], None, grads,
+            self._bn_bwd(c, name + ".5", gT, 64 * T, o, Act(c.catT, 64 * T, 0, 64 * T), o, 64, c.bn2[:, o:o + 64], None, grads,
                          "", out_amax=am_gT, gnames=(name + ".5.weight", name + ".5.bias"))
             DZ2 = Act(gT, 64 * T, o, 64, amax=am_gT)
             v1 = c.bn1[t]
             A1 = Act(c.z1[t], 64, 0, 64, v1[0], v1[1], v1[2], v1[3], amax=c.am_z1[t])
             self._wgrad(c, A1, DZ2, seq[4], grads, name + ".4", False)
+            if not on("dgrad", name + ".4"):
+                continue
             g1 = buf(64)
             self._dgrad(c, DZ2, seq[4], 0, 64, g1, 64, 0, mask=A1, bn=True)
-            self._bn_bwd(c, g1, 64, 0, Act(c.z1[t], 64, 0, 64), 0, 64, v1, None, grads, "",
+            self._bn_bwd(c, name + ".2", g1, 64, 0, Act(c.z1[t], 64, 0, 64), 0, 64, v1, None, grads, "",
                          gnames=(name + ".2.weight", name + ".2.bias"))
-            ns = max(1, min(B * (8 if H > 64 else 1), 2048))     # (image split, row band) entries
-            sslab = torch.empty(ns * 64 * 27, dtype=torch.float32, device=dev)
-            call("tsr_stem_wgrad_b16" if self.io16 else "tsr_stem_wgrad", ptr(c.x), _I(c.x.shape[1]), _I(m.axisCnt * t),
-                 _I(c.hin), _I(c.win), _I(m.scale_factor), ptr(g1), _I(64), _I(0), ptr(sslab), _I(ns), _I(B), stream())
-            gw = grads.dest(name + ".1.weight", seq[1].weight.shape)
-            call("tsr_reduce_splits", ptr(sslab), ptr(gw), _L(64 * 27), _I(ns), _F(1.0), stream())
-            grads.put(name + ".1.weight", gw)
-            if dx is not None:
+            if on("stem_wgrad", name + ".1"):
+                ns = max(1, min(B * (8 if H > 64 else 1), 2048))     # (image split, row band) entries
+                sslab = torch.empty(ns * 64 * 27, dtype=torch.float32, device=dev)
+                call("tsr_stem_wgrad_b16" if self.io16 else "tsr_stem_wgrad", ptr(c.x), _I(c.x.shape[1]),
+                     _I(m.axisCnt * t), _I(c.hin), _I(c.win), _I(m.scale_factor), ptr(g1), _I(64), _I(0), ptr(sslab),
+                     _I(ns), _I(B), stream())
+                gw = grads.dest(name + ".1.weight", seq[1].weight.shape)
+                call("tsr_reduce_splits", ptr(sslab), ptr(gw), _L(64 * 27), _I(ns), _F(1.0), stream())
+                grads.put(name + ".1.weight", gw)
+            if on("stem_dgrad", name + ".1"):
                 self._stem_dgrad(c, seq[1].weight, g1, 64, 0, dx, m.axisCnt * t, int(t == 0))
         return grads.finalize()
 
@@ -769,6 +950,7 @@ class TactileSRTrainFn(torch.autograd.Function):
     def forward(ctx, engine: TrainEngine, names, x, *params):
         out, c = engine.forward(x)
         c.want_dx = bool(ctx.needs_input_grad[2])      # d loss / d taxels only when the caller's input requires grad
+        c.want = frozenset(n for n, need in zip(names, ctx.needs_input_grad[3:]) if need)      # one flag per parameter
         ctx.engine, ctx.c, ctx.names = engine, c, names
         if any(ctx.needs_input_grad):
             from ..ddp import note_forward
@@ -781,10 +963,10 @@ class TactileSRTrainFn(torch.autograd.Function):
         grads = ctx.engine.backward(c, dout)
         dx, c.dx = c.dx, None
         ctx.c = None
-        missing = [n for n in ctx.names if n not in grads]
+        missing = [n for n in ctx.names if n in c.want and n not in grads]
         if missing:
             raise _lib.TactileSRHipError(f"backward produced no gradient for {missing[:4]}...")
-        return (None, None, dx) + tuple(grads[n] for n in ctx.names)
+        return (None, None, dx) + tuple(grads.get(n) if n in c.want else None for n in ctx.names)
 
 
 class BlockEngine(TrainEngine):
@@ -811,6 +993,8 @@ class BlockEngine(TrainEngine):
         B, C, H, W = x.shape
         dev = x.device
         c = self._new_ctx(B, H, W, dev)
+        c.want = self._want_default(self.block.named_parameters())      # (BlockTrainFn: what autograd asks for instead)
+        c.want_dx = True
         self._weight_scales(c)
         new_amax = self._amax_pool(dev)
 
@@ -832,7 +1016,10 @@ class BlockEngine(TrainEngine):
         from ..ddp import GradSink
         dev = dout.device
         B, H, W = c.B, c.H, c.W
-        grads = GradSink(self, dict(self.block.named_parameters()), dev, token=c)
+        c.live = {r.key for r in block_backward_plan(self.kind, c.want, c.want_dx)}
+        grads = GradSink(self, dict(self.block.named_parameters()), dev, token=c, want=c.want)
+        if not c.live:
+            return None, grads.finalize()
         new_amax = self._amax_pool(dev)
 
         def buf(ch):
@@ -849,7 +1036,7 @@ class BlockEngine(TrainEngine):
             dx = self._msrb_bwd(c, c.s, self.block, "", dpre, grads, new_amax, buf, mask_input=False)
         else:
             dx = self._res_bwd(c, c.s, self.block, "", dpre, grads, new_amax, buf, mask_input=False)
-        return from_cb16(dx.buf, B, 64, H, W), grads.finalize()
+        return from_cb16(dx.buf, B, 64, H, W) if dx is not None else None, grads.finalize()
 
 
 class BlockTrainFn(torch.autograd.Function):
@@ -858,6 +1045,8 @@ class BlockTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, engine: BlockEngine, names, x, *params):
         out, c = engine.forward(x)
+        c.want_dx = bool(ctx.needs_input_grad[2])      # the block input's gradient only when it is asked for
+        c.want = frozenset(n for n, need in zip(names, ctx.needs_input_grad[3:]) if need)
         ctx.engine, ctx.c, ctx.names = engine, c, names
         if any(ctx.needs_input_grad):
             from ..ddp import note_forward
@@ -866,9 +1055,10 @@ class BlockTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        dx, grads = ctx.engine.backward(ctx.c, dout)
+        c = ctx.c
+        dx, grads = ctx.engine.backward(c, dout)
         ctx.c = None
-        missing = [n for n in ctx.names if n not in grads]
+        missing = [n for n in ctx.names if n in c.want and n not in grads]
         if missing:
             raise _lib.TactileSRHipError(f"backward produced no gradient for {missing[:4]}...")
-        return (None, None, dx) + tuple(grads[n] for n in ctx.names)
+        return (None, None, dx) + tuple(grads.get(n) if n in c.want else None for n in ctx.names)

@@ -101,14 +101,26 @@ def load_checkpoint(path: str, model, optimizer=None, lr_scheduler=None, num_gpu
     return ck
 
 
-def model_param_init(seqs_model, single_frame_state_dict, make_single_model):
+def model_param_init(seqs_model, single_frame_state_dict, make_single_model, freeze=False):
     """The Seqs trainer's weight transplant (train/tactileSRSeqs_train.py:43-59): build the single-frame
     model, load its checkpointed weights, and REPLACE the two feature-extraction submodules of the
     multi-frame model by it.  As in the reference, an optimizer created before this call keeps pointing at
-    the discarded modules, so the transplanted blocks stay frozen (only BN running stats move)."""
+    the discarded modules, so the transplanted blocks are never stepped (only BN running stats move).
+
+    ``freeze=False`` (default) is the reference's behaviour: the transplanted parameters still require grad, every
+    step computes their gradients, and -- no optimizer clearing them -- these pile up in ``.grad`` and enter
+    ``clip_grad_norm_(model.parameters(), c)``.  ``freeze=True`` calls ``requires_grad_(False)`` on the parameters of the
+    two transplanted containers: the train step then skips every backward launch that only served them and those
+    gradients do not exist, so they are no part of a clipping norm either (the norm is over the parameters that
+    train); the fused clip applies and ``GraphedTrainStep(clip_grad_norm>0)`` accepts the flow.  The BatchNorm layers of
+    the frozen blocks stay in batch-statistics mode either way."""
     single = make_single_model()
     single.load_state_dict(single_frame_state_dict, strict=False)
     single = single.to(next(seqs_model.parameters()).device)
     seqs_model.patternFeatureExtra_layer = single.patternFeatureExtra_layer
     seqs_model.forceFeatureExtra_layer = single.forceFeatureExtra_layer
+    if freeze:
+        for container in (seqs_model.patternFeatureExtra_layer, seqs_model.forceFeatureExtra_layer):
+            for p in container.parameters():
+                p.requires_grad_(False)
     return seqs_model

@@ -17,7 +17,8 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
   reads them from a device buffer that is rewritten before every replay from the optimizer's CURRENT ``group["lr"]``
   (an lr scheduler works unchanged) and the advanced ``state["step"]``.  The step then has the eager step's results
   bit for bit, checkpoints included.
-* Recapture: when ``train_impl``, the parameter / buffer / optimizer-state / gradient-arena addresses, the loss
+* Recapture: when ``train_impl``, the parameter / buffer / optimizer-state / gradient-arena addresses, the set of
+  parameters that require grad (the captured backward holds only the launches a trainable parameter depends on), the loss
   config, the optimizer's baked constants (``betas``, ``eps``, ``weight_decay``) or ``clip_grad_norm`` change, the
   graph is dropped and the next ``warmup`` calls run eagerly again before a new capture.  ``captures`` counts the captures.
 * The returned ``total_loss`` is the graph's static OUTPUT BUFFER (like ``GraphedForward``): the next call overwrites
@@ -35,11 +36,12 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
   its own gradients.  ``c`` is baked into the graph like ``betas`` / ``eps`` / ``weight_decay``: assigning another
   ``gstep.clip_grad_norm`` drops the graph and recaptures.  Clipping needs the fused path's condition: every trainable
   model parameter is stepped by the optimizer (refused otherwise, e.g. the Seqs transplant, whose new parameters are
-  not in the optimizer).  ``c <= 0`` (the default) captures the step as before.
+  not in the optimizer; ``model_param_init(..., freeze=True)`` freezes them and the flow is accepted).  ``c <= 0`` (the
+  default) captures the step as before.
 * Refused (``TactileSRHipError``): eval mode, a batch whose shape / dtype differs from the first call's, an attached
   ``GradSync`` (no collectives inside a graph), ``engine.profile`` / ``engine.debug`` / ``engine.keep_ctx``, an
-  optimizer other than ``tactilesr_amd.optim.Adam``, a model not on a ROCm device, clipping where a trainable model
-  parameter is not in the optimizer.
+  optimizer other than ``tactilesr_amd.optim.Adam``, a model not on a ROCm device, a model without a trainable
+  parameter, clipping where a trainable model parameter is not in the optimizer.
 """
 from __future__ import annotations
 
@@ -92,12 +94,15 @@ class GraphedTrainStep:
                        for g in opt.param_groups)
         return (m.train_impl, id(arena), arena.flat.data_ptr() if arena is not None else 0,
                 tuple(t.data_ptr() for t in m.parameters()), tuple(b.data_ptr() for b in m.buffers()), groups,
-                tuple(self.config[k] for k in _CONFIG_KEYS), self.clip_grad_norm)
+                tuple(self.config[k] for k in _CONFIG_KEYS), self.clip_grad_norm,
+                tuple(p.requires_grad for p in m.parameters()))      # the captured backward holds the trainable set's launches
 
     def _check(self, LR, HR) -> None:
         m = self.model
         if not m.training:
             raise TactileSRHipError("GraphedTrainStep replays the TRAIN step: the model is in eval mode")
+        if not any(p.requires_grad for p in m.parameters()):
+            raise TactileSRHipError("GraphedTrainStep: no model parameter requires grad (nothing to train)")
         sig = (tuple(LR.shape), LR.dtype, tuple(HR.shape), HR.dtype)
         if self._sig is None:
             self._sig = sig

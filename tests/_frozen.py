@@ -1,0 +1,124 @@
+"""Shared by the frozen-parameter tests (tests/test_frozen_cpu.py, tests/test_gpu_frozen.py): the parameter names of a
+TactileSR / MSRB / ResBlock derived from the architecture alone, the named freeze patterns of the issue, and what a backward
+plan (tactilesr_amd.model._train.backward_plan) implies for the entry points a backward calls.  Host only."""
+from collections import Counter
+
+MSRB_CONVS = ("conv_3_1", "conv_5_1", "conv_3_2", "conv_5_2")
+
+
+def msrb_names(p=""):
+    out = []
+    for c in MSRB_CONVS:
+        out += [f"{p}{c}.0.weight", f"{p}{c}.0.bias", f"{p}{c}.1.weight", f"{p}{c}.1.bias"]
+    return out + [p + "confusion.weight", p + "confusion.bias"]
+
+
+def res_names(p=""):
+    return [p + "conv1.weight", p + "conv1.bias", p + "conv2.weight", p + "conv2.bias"]
+
+
+def param_names(T, M, R):
+    """Every parameter name of TactileSR(seqsCnt=T, patternFeatureExtraLayerCnt=M, forceFeatureExtraLayerCnt=R)."""
+    out = []
+    for t in range(T):
+        p = f"inputLayer_pattern_list.{t}."
+        out += [p + "1.weight", p + "2.weight", p + "2.bias", p + "4.weight", p + "5.weight", p + "5.bias"]
+    out += ["inputContact_layer.0.weight", "inputContact_layer.1.weight", "inputContact_layer.1.bias"]
+    for i in range(M):
+        out += msrb_names(f"patternFeatureExtra_layer.{i}.")
+    out += ["input_layer_force.1.weight"]
+    for i in range(R):
+        out += res_names(f"forceFeatureExtra_layer.{i}.")
+    return out + ["output_layer.0.weight", "output_layer.2.weight"]
+
+
+def is_bn(name):
+    """BatchNorm affine parameters: index 1 of an MSRB conv + BN pair, indices 2 / 5 of a stem, inputContact_layer.1."""
+    parts = name.split(".")
+    if parts[0] == "patternFeatureExtra_layer":
+        return parts[2] in MSRB_CONVS and parts[3] == "1"
+    if parts[0] == "inputLayer_pattern_list":
+        return parts[2] in ("2", "5")
+    return name.startswith("inputContact_layer.1.")
+
+
+def is_trunk(name):
+    """The two containers the Seqs trainer transplants (reference train/tactileSRSeqs_train.py:43-59)."""
+    return name.startswith(("patternFeatureExtra_layer.", "forceFeatureExtra_layer."))
+
+
+# name -> (want-set from the full name list, whether the taxels ask for a gradient)
+PATTERNS = {
+    "all": lambda names: (frozenset(names), False),
+    "head": lambda names: (frozenset(n for n in names if n.startswith("output_layer.")), False),
+    "trunk": lambda names: (frozenset(n for n in names if not is_trunk(n)), False),
+    "all_frozen_dx": lambda names: (frozenset(), True),
+    "middle_msrb": lambda names: (frozenset(n for n in names if n.startswith("patternFeatureExtra_layer.1.")), False),
+    "bn_only": lambda names: (frozenset(n for n in names if is_bn(n)), False),
+    "res_bias": lambda names: (frozenset(n for n in names if not (n.startswith("forceFeatureExtra_layer.0.conv")
+                                                                   and n.endswith(".weight"))), True),
+}
+
+
+def production_order(plan, want):
+    """The wanted parameter gradients in the order the plan's launches produce them: the gradient arena's layout."""
+    return [n for r in plan for n in r.params if n in want]
+
+
+def expected_calls(plan, want):
+    """Entry-point families a backward following `plan` calls, and how often (the b16 forms count with the fp32 ones)."""
+    k = Counter(r.kind for r in plan)
+    exp = Counter()
+    exp["head_bwd"] = k["head_bwd"]
+    exp["head_dgrad"] = k["head_dgrad"]
+    exp["wgrad"] = k["wgrad"]
+    exp["conv_ex"] = k["dgrad"]                    # the only tsr_conv2d_ex launches of a backward are its dgrads
+    exp["pack_dgrad"] = k["dgrad"]                 # one flipped weight pack per dgrad
+    exp["bn_bwd_finalize"] = k["bn_bwd_finalize"]
+    exp["bn_bwd_apply"] = k["bn_bwd_apply"]
+    exp["stem_wgrad"] = k["stem_wgrad"]
+    exp["stem_dgrad"] = k["stem_dgrad"]
+    # tsr_reduce_splits: once per WANTED parameter gradient that a split-slab launch produces
+    exp["reduce_splits"] = sum(1 for r in plan if r.kind in ("head_bwd", "wgrad", "stem_wgrad") for n in r.params if n in want)
+    return +exp
+
+
+FAMILY = (("tsr_head_bwd", "head_bwd"), ("tsr_head_dgrad", "head_dgrad"), ("tsr_conv2d_wgrad", "wgrad"),
+          ("tsr_pack_conv_weight_dgrad", "pack_dgrad"), ("tsr_bn_bwd_finalize", "bn_bwd_finalize"),
+          ("tsr_bn_bwd_apply", "bn_bwd_apply"), ("tsr_stem_wgrad", "stem_wgrad"), ("tsr_stem_dgrad", "stem_dgrad"),
+          ("tsr_reduce_splits", "reduce_splits"))
+
+
+def family(entry_point):
+    for prefix, fam in FAMILY:
+        if entry_point.startswith(prefix):
+            return fam
+    return None
+
+
+class CallCounter:
+    """Counts what `_train.call` / `_train.conv_ex` are asked to launch while it is active (they stay in effect)."""
+
+    def __init__(self, train_mod):
+        self.mod = train_mod
+        self.counts = Counter()
+
+    def __enter__(self):
+        self._call, self._conv_ex = self.mod.call, self.mod.conv_ex
+
+        def call(name, *args):
+            fam = family(name)
+            if fam is not None:
+                self.counts[fam] += 1
+            return self._call(name, *args)
+
+        def conv_ex(**kw):
+            self.counts["conv_ex"] += 1
+            return self._conv_ex(**kw)
+
+        self.mod.call, self.mod.conv_ex = call, conv_ex
+        return self
+
+    def __exit__(self, *exc):
+        self.mod.call, self.mod.conv_ex = self._call, self._conv_ex
+        return False
