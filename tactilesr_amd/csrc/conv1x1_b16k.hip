@@ -14,6 +14,7 @@
 //     at its end: entries = workgroups (tsr_conv2d_slab_entries_ex, nsplit = -3, ks = 1).
 #include "tsr_common.h"
 #include "conv_args.h"
+#include "conv_host.h"
 #include "tactilesr_hip.h"
 
 typedef __bf16 xb16x8 __attribute__((ext_vector_type(8)));

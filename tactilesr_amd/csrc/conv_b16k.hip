@@ -28,7 +28,7 @@
 #include "tsr_common.h"
 #include "conv_args.h"
 #include "tactilesr_hip.h"
-#include <type_traits>
+#include "conv_host.h"
 
 typedef __bf16 kb16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 kb16x4 __attribute__((ext_vector_type(4)));
@@ -445,7 +445,7 @@ template <> struct B16KJobs<3> {       // HH = 10: next rows 0..5 -> never-used 
 };
 
 // NW = waves = images per workgroup (4: two workgroups per CU; 8: one 512-thread workgroup per CU whose weight slab serves 512
-// pixels -- see B16K_LAUNCH).
+// pixels -- see b16k_launch).
 // Barrier steps of a channel block.  Plain / fused: one tap per step.  Pair form: the 16 outer taps carry half the MFMAs (the 3x3
 // conv has no weight there), so two CONSECUTIVE outer taps share a step -- 8 double steps + the 9 inner taps = 17 steps of 32
 // MFMAs per wave instead of 25 -- and a weight slab: [k group][64 channels of the 5x5 conv at the second tap | at the first
@@ -765,9 +765,22 @@ extern "C" long long tsr_conv_weight_b16k_pair_elems(int cin) { return (long lon
 #ifndef TSR_B16K_NW
 #define TSR_B16K_NW 4
 #endif
-#define B16K_LAUNCH(KS_, COUT_, MODE_)                                                                         \
-  hipLaunchKernelGGL((conv_b16k_kernel<KS_, COUT_, MODE_, TSR_B16K_NW>),                                       \
+int tsr_conv_b16k_images() { return TSR_B16K_NW; }      // = statistics-slab entries per workgroup (tsr_conv2d_slab_entries_ex)
+
+template <int KS, int COUT, int MODE> static int b16k_launch(const ConvArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL((conv_b16k_kernel<KS, COUT, MODE, TSR_B16K_NW>),
                      dim3(((a.B + TSR_B16K_NW - 1) / TSR_B16K_NW) * a.tiles_x * a.tiles_y), dim3(TSR_B16K_NW * 64), 0, st, a);
+  return tsr_check_launch();
+}
+// (cout, ks) ladder of the 3x3 / 5x5 kernel (it has no 1x1 form)
+template <int MODE> static int b16k_dispatch(const ConvArgs& a, int cout, int ks, hipStream_t st) {
+  return for_cout_ks<128>(cout, ks, [&](auto CO, auto KS) {
+    if constexpr (decltype(KS)::value > 1) return b16k_launch<decltype(KS)::value, decltype(CO)::value, MODE>(a, st);
+    else return (int)TSR_ERR_ARG;
+  });
+}
+// 32-bit halo offsets inside a 4-image group
+static bool b16k_offsets_ok(int in_ctot, int H, int W) { return (long long)4 * in_ctot * H * W * 2 < 0x7fffffffLL; }
 static bool b16k_shape_ok(int cout, int cin, int ks) {
   return (cout == 64 || cout == 128) && cin > 0 && (cin & 31) == 0 && (ks == 3 || ks == 5);
 }
@@ -775,19 +788,15 @@ static bool b16k_shape_ok(int cout, int cin, int ks) {
 extern "C" int tsr_pack_conv_weight_b16k(const float* w_oihw, void* w_packed, int cout, int cin, int ks, void* stream) {
   // (ks = 1: the forward of a 1x1 conv with 64 output channels, conv1x1_b16k.hip -- the same slab layout with one tap)
   if (!w_oihw || !w_packed || !(b16k_shape_ok(cout, cin, ks) || (ks == 1 && cout == 64 && cin > 0 && (cin & 31) == 0))) return TSR_ERR_ARG;
-  const size_t total = (size_t)cout * cin * ks * ks;
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_b16k_kernel, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0, (hipStream_t)stream, w_oihw,
+  hipLaunchKernelGGL(pack_b16k_kernel, pack_grid((size_t)cout * cin * ks * ks), dim3(256), 0, (hipStream_t)stream, w_oihw,
                      (__bf16*)w_packed, cout, cin, ks * ks);
   return tsr_check_launch();
 }
 
 extern "C" int tsr_pack_conv_weight_b16k_pair(const float* w128_oihw5, void* w_packed, int cin, void* stream) {
   if (!w128_oihw5 || !w_packed || !b16k_shape_ok(128, cin, 5)) return TSR_ERR_ARG;
-  const size_t total = (size_t)tsr_conv_weight_b16k_pair_elems(cin);
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_b16k_pair_kernel, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0, (hipStream_t)stream, w128_oihw5,
-                     (__bf16*)w_packed, cin);
+  hipLaunchKernelGGL(pack_b16k_pair_kernel, pack_grid((size_t)tsr_conv_weight_b16k_pair_elems(cin)), dim3(256), 0,
+                     (hipStream_t)stream, w128_oihw5, (__bf16*)w_packed, cin);
   return tsr_check_launch();
 }
 
@@ -806,10 +815,8 @@ extern "C" int tsr_conv2d_ex_fwd1x1_b16k(int cout, int cin) { return cout == 64 
 extern "C" int tsr_pack_conv_weight_dgrad_b16k(const float* w_oihw, void* w_packed, int cout, int cin, int ks, int ci0, int nprime,
                                                void* stream) {
   if (!w_oihw || !w_packed || !tsr_conv2d_ex_dgrad_b16k(nprime, cout, ks) || ci0 < 0 || ci0 + nprime > cin) return TSR_ERR_ARG;
-  const size_t total = (size_t)nprime * cout * ks * ks;
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_b16k_dgrad_kernel, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0, (hipStream_t)stream, w_oihw,
-                     (__bf16*)w_packed, cout, cin, ks * ks, ci0, nprime);
+  hipLaunchKernelGGL(pack_b16k_dgrad_kernel, pack_grid((size_t)nprime * cout * ks * ks), dim3(256), 0, (hipStream_t)stream,
+                     w_oihw, (__bf16*)w_packed, cout, cin, ks * ks, ci0, nprime);
   return tsr_check_launch();
 }
 
@@ -817,40 +824,19 @@ extern "C" int tsr_pack_conv_weight_dgrad_b16k(const float* w_oihw, void* w_pack
 // stored block output, a materialised activation): epi_mode 0 = out = act(acc * scale + shift + res) (the forward weight
 // pack, or the dgrad pack for an unmasked partial gradient), 1 = raw output + Welford partials (forward pack), 2 = the masked
 // dgrad (dgrad pack).  nsplit = -4 (`pair`): epi_mode 1 of the stage-1 pair (one 128-channel output, two convs).
-int tsr_dgrad1x1_b16k(const ConvArgs& a, hipStream_t st);       // conv1x1_b16k.hip
-int tsr_fwd1x1_b16k(const ConvArgs& a, int cout, hipStream_t st);
 int tsr_conv_b16k_ex(const ConvArgs& a, int cout, int ks, bool pair, hipStream_t st) {
   // the forward of a 1x1 conv with 64 output channels on a VIRTUAL input (the only form here that takes an input transform)
   if (ks == 1 && cout == 64 && a.epi_mode == 0 && !pair) return tsr_fwd1x1_b16k(a, cout, st);
-  if (!tsr_conv2d_ex_dgrad_b16k(cout, a.cin, ks) || a.in_scale || a.res_scale ||
-      (long long)4 * a.in_ctot * a.H * a.W * 2 >= 0x7fffffffLL)
+  if (!tsr_conv2d_ex_dgrad_b16k(cout, a.cin, ks) || a.in_scale || a.res_scale || !b16k_offsets_ok(a.in_ctot, a.H, a.W))
     return TSR_ERR_ARG;
   if (ks == 1) return pair ? TSR_ERR_ARG : tsr_dgrad1x1_b16k(a, st);
   if (pair) {      // nsplit = -4: conv_3_1 || conv_5_1 of an MSRB in train mode (weights: tsr_pack_conv_weight_b16k_pair)
     if (ks != 5 || cout != 128 || a.epi_mode != 1 || !a.slab || !a.slab_cnt) return TSR_ERR_ARG;
-    B16K_LAUNCH(5, 128, B16K_PAIR_TRAIN)
-    return tsr_check_launch();
+    return b16k_launch<5, 128, B16K_PAIR_TRAIN>(a, st);
   }
-#define B16K_LAUNCH_C(MODE_)                                   \
-  {                                                            \
-    if (cout == 128) {                                         \
-      if (ks == 3) B16K_LAUNCH(3, 128, MODE_)                  \
-      else B16K_LAUNCH(5, 128, MODE_)                          \
-    } else {                                                   \
-      if (ks == 3) B16K_LAUNCH(3, 64, MODE_)                   \
-      else B16K_LAUNCH(5, 64, MODE_)                           \
-    }                                                          \
-  }
-  if (a.epi_mode == 2) {
-    B16K_LAUNCH_C(B16K_DGRAD)
-  } else if (a.epi_mode == 1) {
-    if (!a.slab || !a.slab_cnt) return TSR_ERR_ARG;
-    B16K_LAUNCH_C(B16K_TRAIN)
-  } else {
-    B16K_LAUNCH_C(B16K_PLAIN)
-  }
-#undef B16K_LAUNCH_C
-  return tsr_check_launch();
+  if (a.epi_mode == 2) return b16k_dispatch<B16K_DGRAD>(a, cout, ks, st);
+  if (a.epi_mode == 1) return (!a.slab || !a.slab_cnt) ? TSR_ERR_ARG : b16k_dispatch<B16K_TRAIN>(a, cout, ks, st);
+  return b16k_dispatch<B16K_PLAIN>(a, cout, ks, st);
 }
 
 extern "C" int tsr_pack_w2_b16k(const float* w2_64x128, void* w_packed, void* stream) {
@@ -860,40 +846,26 @@ extern "C" int tsr_pack_w2_b16k(const float* w2_64x128, void* w_packed, void* st
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
-static int b16k_fill(ConvArgs& a, const void* in, int in_ctot, int in_coff, int cin, const void* w_packed, int cout,
-                     const float* scale, const float* shift, const void* res, int res_ctot, int res_coff, void* out,
-                     int out_ctot, int out_coff, int out_ch, int relu, int B, int H, int W) {
-  if (!in || !w_packed || !out || B <= 0 || H <= 0 || W <= 0) return TSR_ERR_ARG;
-  if ((in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || in_coff < 0 || out_coff < 0 ||
-      in_coff + cin > in_ctot || out_coff + out_ch > out_ctot)
+// conv_fill + this family's own rules: the shapes the kernel takes (which imply conv_fill's cin > 0 and cin % 16 == 0) and
+// the 32-bit halo-offset limit
+static int b16k_check_fill(ConvArgs& a, const void* in, int in_ctot, int in_coff, int cin, const void* w_packed, int cout,
+                           int ks, const float* scale, const float* shift, const void* res, int res_ctot, int res_coff,
+                           void* out, int out_ctot, int out_coff, int out_ch, int relu, int B, int H, int W) {
+  if (!b16k_shape_ok(cout, cin, ks)) return TSR_ERR_ARG;
+  if (conv_fill(a, in, in_ctot, in_coff, cin, w_packed, scale, shift, res, res_ctot, res_coff, out, out_ctot, out_coff, out_ch,
+                relu, B, H, W))
     return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + out_ch > res_ctot)) return TSR_ERR_ARG;
-  if ((long long)4 * in_ctot * H * W * 2 >= 0x7fffffffLL) return TSR_ERR_ARG;      // 32-bit halo offsets inside a 4-image group
-  a = ConvArgs{};
-  a.in = (const float*)in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
-  a.wp = (const float*)w_packed; a.scale = scale; a.shift = shift;
-  a.res = (const float*)res; a.res_ctot = res_ctot; a.res_coff = res_coff;
-  a.out = (float*)out; a.out_ctot = out_ctot; a.out_coff = out_coff; a.relu = relu;
-  a.B = B; a.H = H; a.W = W;
-  a.tiles_x = (W + 7) / 8; a.tiles_y = (H + 7) / 8;
-  (void)cout;
-  return TSR_OK;
+  return b16k_offsets_ok(in_ctot, H, W) ? TSR_OK : TSR_ERR_ARG;
 }
 
 extern "C" int tsr_conv2d_fwd_b16k(const void* in, int in_ctot, int in_coff, int cin, const void* w_packed, int cout, int ks,
                                    const float* scale, const float* shift, const void* res, int res_ctot, int res_coff,
                                    void* out, int out_ctot, int out_coff, int relu, int B, int H, int W, void* stream) {
-  if (!b16k_shape_ok(cout, cin, ks)) return TSR_ERR_ARG;
   ConvArgs a;
-  const int rc = b16k_fill(a, in, in_ctot, in_coff, cin, w_packed, cout, scale, shift, res, res_ctot, res_coff, out, out_ctot,
-                           out_coff, cout, relu, B, H, W);
-  if (rc != TSR_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (cout == 64 && ks == 3) B16K_LAUNCH(3, 64, B16K_PLAIN)
-  else if (cout == 64) B16K_LAUNCH(5, 64, B16K_PLAIN)
-  else if (ks == 3) B16K_LAUNCH(3, 128, B16K_PLAIN)
-  else B16K_LAUNCH(5, 128, B16K_PLAIN)
-  return tsr_check_launch();
+  if (b16k_check_fill(a, in, in_ctot, in_coff, cin, w_packed, cout, ks, scale, shift, res, res_ctot, res_coff, out, out_ctot,
+                      out_coff, cout, relu, B, H, W))
+    return TSR_ERR_ARG;
+  return b16k_dispatch<B16K_PLAIN>(a, cout, ks, (hipStream_t)stream);
 }
 
 // Stage-2 convolution of an MSRB (128 -> 128, BatchNorm + ReLU) with its half of the 1x1 `confusion` fused: out / res
@@ -902,16 +874,13 @@ extern "C" int tsr_conv2d_fwd_b16k_fuse1x1(const void* in, int in_ctot, int in_c
                                            const float* scale, const float* shift, int relu, const void* w2_packed,
                                            const float* shift2, const void* res, int res_ctot, int res_coff, void* out,
                                            int out_ctot, int out_coff, int relu2, int B, int H, int W, void* stream) {
-  if (!b16k_shape_ok(128, cin, ks) || !w2_packed) return TSR_ERR_ARG;
   ConvArgs a;
-  const int rc = b16k_fill(a, in, in_ctot, in_coff, cin, w_packed, 128, scale, shift, res, res_ctot, res_coff, out, out_ctot,
-                           out_coff, 64, relu, B, H, W);
-  if (rc != TSR_OK) return rc;
+  if (!w2_packed || b16k_check_fill(a, in, in_ctot, in_coff, cin, w_packed, 128, ks, scale, shift, res, res_ctot, res_coff, out,
+                                    out_ctot, out_coff, 64, relu, B, H, W))
+    return TSR_ERR_ARG;
   a.w2 = w2_packed; a.w2_inv_scale = 1.f; a.shift2 = shift2; a.relu2 = relu2;
   hipStream_t st = (hipStream_t)stream;
-  if (ks == 3) B16K_LAUNCH(3, 128, B16K_FUSED)
-  else B16K_LAUNCH(5, 128, B16K_FUSED)
-  return tsr_check_launch();
+  return ks == 3 ? b16k_launch<3, 128, B16K_FUSED>(a, st) : b16k_launch<5, 128, B16K_FUSED>(a, st);
 }
 
 // Stage-1 pair of an MSRB: w_packed = tsr_pack_conv_weight_b16k_pair(cat([zero-pad(w3 -> 5x5), w5]), cin); scale / shift
@@ -919,12 +888,9 @@ extern "C" int tsr_conv2d_fwd_b16k_fuse1x1(const void* in, int in_ctot, int in_c
 extern "C" int tsr_conv2d_fwd_b16k_pair(const void* in, int in_ctot, int in_coff, int cin, const void* w_packed,
                                         const float* scale, const float* shift, void* out, int out_ctot, int out_coff,
                                         int relu, int B, int H, int W, void* stream) {
-  if (!b16k_shape_ok(128, cin, 5)) return TSR_ERR_ARG;
   ConvArgs a;
-  const int rc = b16k_fill(a, in, in_ctot, in_coff, cin, w_packed, 128, scale, shift, nullptr, 0, 0, out, out_ctot, out_coff,
-                           128, relu, B, H, W);
-  if (rc != TSR_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  B16K_LAUNCH(5, 128, B16K_PAIR)
-  return tsr_check_launch();
+  if (b16k_check_fill(a, in, in_ctot, in_coff, cin, w_packed, 128, 5, scale, shift, nullptr, 0, 0, out, out_ctot, out_coff, 128,
+                      relu, B, H, W))
+    return TSR_ERR_ARG;
+  return b16k_launch<5, 128, B16K_PAIR>(a, (hipStream_t)stream);
 }

@@ -21,6 +21,7 @@
 
 #include "conv_args.h"
 #include "conv_epilogue.h"
+#include "conv_host.h"
 
 // EXT = training-path extensions compiled in (input/residual transforms, epi_mode 1/2);
 // PF  = prefetch the next channel block's halo slab into registers during the current block.
@@ -232,47 +233,23 @@ __global__ void pack_conv_weight_dgrad_kernel(const float* __restrict__ w, float
 
 extern "C" int tsr_pack_conv_weight_dgrad(const float* w_oihw, float* w_packed, int cout, int cin, int ks,
                                           int ci0, int nprime, void* stream) {
-  if (!w_oihw || !w_packed || (cout & 15) || (nprime != 64 && nprime != 128) || ci0 < 0 || ci0 + nprime > cin ||
-      (ks != 1 && ks != 3 && ks != 5))
-    return TSR_ERR_ARG;
-  const size_t total = (size_t)nprime * cout * ks * ks;
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_conv_weight_dgrad_kernel, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0,
+  if (!w_oihw || !w_packed || !pack_dgrad_shape_ok(cout, cin, ks, ci0, nprime)) return TSR_ERR_ARG;
+  hipLaunchKernelGGL(pack_conv_weight_dgrad_kernel, pack_grid((size_t)nprime * cout * ks * ks), dim3(256), 0,
                      (hipStream_t)stream, w_oihw, w_packed, cout, cin, ks, ci0, nprime);
   return tsr_check_launch();
 }
 
 extern "C" int tsr_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin, int ks,
                                     void* stream) {
-  if (!w_oihw || !w_packed || cin <= 0 || (cin & 15) || (cout != 64 && cout != 128) ||
-      (ks != 1 && ks != 3 && ks != 5))
-    return TSR_ERR_ARG;
-  const size_t total = (size_t)cout * cin * ks * ks;
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0,
+  if (!w_oihw || !w_packed || !pack_shape_ok(cout, cin, ks)) return TSR_ERR_ARG;
+  hipLaunchKernelGGL(pack_conv_weight_kernel, pack_grid((size_t)cout * cin * ks * ks), dim3(256), 0,
                      (hipStream_t)stream, w_oihw, w_packed, cout, cin, ks);
   return tsr_check_launch();
 }
 
 template <bool EXT>
 static int dispatch_conv(const ConvArgs& a, int cout, int ks, hipStream_t st) {
-  if (cout == 64) {
-    if (ks == 1) return launch_conv<1, 64, EXT>(a, st);
-    if (ks == 3) return launch_conv<3, 64, EXT>(a, st);
-    if (ks == 5) return launch_conv<5, 64, EXT>(a, st);
-  } else if (cout == 128) {
-    if (ks == 1) return launch_conv<1, 128, EXT>(a, st);
-    if (ks == 3) return launch_conv<3, 128, EXT>(a, st);
-    if (ks == 5) return launch_conv<5, 128, EXT>(a, st);
-  }
-  return TSR_ERR_ARG;
-}
-
-static int check_slices(int cin, int in_ctot, int in_coff, int cout, int out_ctot, int out_coff) {
-  if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + cout > out_ctot)
-    return TSR_ERR_ARG;
-  return TSR_OK;
+  return for_cout_ks(cout, ks, [&](auto CO, auto KS) { return launch_conv<decltype(KS)::value, decltype(CO)::value, EXT>(a, st); });
 }
 
 extern "C" int tsr_conv2d_fwd(const float* in, int in_ctot, int in_coff, int cin,
@@ -281,20 +258,12 @@ extern "C" int tsr_conv2d_fwd(const float* in, int in_ctot, int in_coff, int cin
                               const float* res, int res_ctot, int res_coff,
                               float* out, int out_ctot, int out_coff, int relu,
                               int B, int H, int W, void* stream) {
-  if (!in || !w_packed || !out || B <= 0 || H <= 0 || W <= 0) return TSR_ERR_ARG;
-  if (check_slices(cin, in_ctot, in_coff, cout, out_ctot, out_coff)) return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
-  ConvArgs a = {};
-  a.in = in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
-  a.wp = w_packed; a.scale = scale; a.shift = shift;
-  a.res = res; a.res_ctot = res_ctot; a.res_coff = res_coff;
-  a.out = out; a.out_ctot = out_ctot; a.out_coff = out_coff; a.relu = relu;
-  a.B = B; a.H = H; a.W = W;
-  a.tiles_x = (W + 7) / 8; a.tiles_y = (H + 7) / 8;
+  ConvArgs a;
+  if (conv_fill(a, in, in_ctot, in_coff, cin, w_packed, scale, shift, res, res_ctot, res_coff, out, out_ctot, out_coff, cout,
+                relu, B, H, W))
+    return TSR_ERR_ARG;
   return dispatch_conv<false>(a, cout, ks, (hipStream_t)stream);
 }
-
-int tsr_conv_f16s_images(int cout, int ks);     // conv_mfma_split16.hip: images per workgroup of the fp16x3 kernel in use
 
 // Number of (workgroup, image) slab entries a tsr_conv2d_ex launch of this shape emits.
 extern "C" int tsr_conv2d_slab_entries(int B, int H, int W) {
@@ -302,22 +271,22 @@ extern "C" int tsr_conv2d_slab_entries(int B, int H, int W) {
 }
 
 // Slab entries a tsr_conv2d_ex launch with these parameters writes: one per (workgroup, image slot).  The fp16-split
-// 3x3 / 5x5 kernels (tsr_conv_f16s_images: 4 images, 2 for the 1x1 and TSR_CONV_K32_256) and every one-plane 3x3 / 5x5 kernel put 4 images in a
-// workgroup, everything else 2 (must match launch_bf16s in conv_mfma_split16.hip).
-int tsr_dgrad1x1_b16k_grid(int B, int H, int W);           // conv1x1_b16k.hip
+// 3x3 / 5x5 kernels (tsr_conv_f16s_images: 4 images, 2 for the 1x1 and TSR_CONV_K32_256) and the one-plane 3x3 / 5x5 kernels of
+// conv_mfma_split16.hip put 4 images in a workgroup (must match launch_bf16s there), conv_b16k's 3x3 / 5x5 launches
+// tsr_conv_b16k_images, everything else 2.
 extern "C" int tsr_conv2d_slab_entries_ex(int B, int H, int W, int cout, int ks, int nsplit) {
   if (nsplit == -3 && ks == 1) return tsr_dgrad1x1_b16k_grid(B, H, W);        // one entry per workgroup of the streaming kernel
-  if (nsplit == -3 || nsplit == -4) nsplit = -1;
-  const int img = nsplit == -2 ? tsr_conv_f16s_images(cout, ks) : ((ks > 1 && (nsplit == 1 || nsplit == -1)) ? 4 : 2);
+  int img = 2;
+  if (nsplit == -2) img = tsr_conv_f16s_images(cout, ks);
+  else if (ks > 1 && (nsplit == -3 || nsplit == -4)) img = tsr_conv_b16k_images();
+  else if (ks > 1 && (nsplit == 1 || nsplit == -1)) img = 4;
   return ((B + img - 1) / img) * ((W + 7) / 8) * ((H + 7) / 8) * img;
 }
 
-int tsr_conv2d_ex_bf16s(const ConvArgs& a, int cout, int ks, int nsplit, hipStream_t st);   // conv_mfma_split16.hip
-
 extern "C" int tsr_conv2d_ex(const tsr_conv_desc* d, void* stream) {
-  if (!d || !d->in || !d->w_packed || !d->out || d->B <= 0 || d->H <= 0 || d->W <= 0) return TSR_ERR_ARG;
-  if (check_slices(d->cin, d->in_ctot, d->in_coff, d->cout, d->out_ctot, d->out_coff)) return TSR_ERR_ARG;
-  if (d->res && ((d->res_ctot & 15) || (d->res_coff & 15) || d->res_coff < 0 || d->res_coff + d->cout > d->res_ctot))
+  ConvArgs a;
+  if (!d || conv_fill(a, d->in, d->in_ctot, d->in_coff, d->cin, d->w_packed, d->scale, d->shift, d->res, d->res_ctot, d->res_coff,
+                      d->out, d->out_ctot, d->out_coff, d->cout, d->relu, d->B, d->H, d->W))
     return TSR_ERR_ARG;
   if (d->epi_mode < 0 || d->epi_mode > 2) return TSR_ERR_ARG;
   if (d->epi_mode == 1 && (!d->slab || !d->slab_cnt)) return TSR_ERR_ARG;
@@ -326,13 +295,6 @@ extern "C" int tsr_conv2d_ex(const tsr_conv_desc* d, void* stream) {
     return TSR_ERR_ARG;
   if ((d->in_scale != nullptr) != (d->in_shift != nullptr)) return TSR_ERR_ARG;
   if ((d->res_scale != nullptr) != (d->res_shift != nullptr)) return TSR_ERR_ARG;
-  ConvArgs a = {};
-  a.in = d->in; a.in_ctot = d->in_ctot; a.in_coff = d->in_coff; a.cin = d->cin;
-  a.wp = d->w_packed; a.scale = d->scale; a.shift = d->shift;
-  a.res = d->res; a.res_ctot = d->res_ctot; a.res_coff = d->res_coff;
-  a.out = d->out; a.out_ctot = d->out_ctot; a.out_coff = d->out_coff; a.relu = d->relu;
-  a.B = d->B; a.H = d->H; a.W = d->W;
-  a.tiles_x = (d->W + 7) / 8; a.tiles_y = (d->H + 7) / 8;
   a.in_scale = d->in_scale; a.in_shift = d->in_shift;
   a.res_scale = d->res_scale; a.res_shift = d->res_shift;
   a.epi_mode = d->epi_mode;

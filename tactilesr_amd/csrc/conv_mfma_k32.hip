@@ -29,6 +29,7 @@
 #include "conv_args.h"
 #include "conv_epilogue16.h"
 #include "conv_fuse1x1_16.h"
+#include "conv_host.h"
 #include "tactilesr_hip.h"
 #include <type_traits>
 
@@ -529,19 +530,14 @@ static int launch_k32(const ConvArgs& a, hipStream_t st) {
   return tsr_check_launch();
 }
 
+template <bool EXT> static int dispatch_k32(const ConvArgs& a, int cout, int ks, hipStream_t st) {
+  return for_cout_ks(cout, ks, [&](auto CO, auto KS) {
+    if constexpr (decltype(KS)::value > 1) return launch_k32<decltype(KS)::value, decltype(CO)::value, EXT>(a, st);
+    else return (int)TSR_ERR_ARG;       // (the kernel has no 1x1 form)
+  });
+}
 int tsr_conv_k32(const ConvArgs& a, int cout, int ks, bool ext, hipStream_t st) {
-  if (ext) {
-    if (cout == 64 && ks == 3) return launch_k32<3, 64, true>(a, st);
-    if (cout == 64 && ks == 5) return launch_k32<5, 64, true>(a, st);
-    if (cout == 128 && ks == 3) return launch_k32<3, 128, true>(a, st);
-    if (cout == 128 && ks == 5) return launch_k32<5, 128, true>(a, st);
-  } else {
-    if (cout == 64 && ks == 3) return launch_k32<3, 64, false>(a, st);
-    if (cout == 64 && ks == 5) return launch_k32<5, 64, false>(a, st);
-    if (cout == 128 && ks == 3) return launch_k32<3, 128, false>(a, st);
-    if (cout == 128 && ks == 5) return launch_k32<5, 128, false>(a, st);
-  }
-  return TSR_ERR_ARG;
+  return ext ? dispatch_k32<true>(a, cout, ks, st) : dispatch_k32<false>(a, cout, ks, st);
 }
 
 // ---- stage-1 pair: channel order and weight pack ---------------------------------------------------------------------
@@ -622,10 +618,8 @@ extern "C" long long tsr_conv_weight_pair_elems(int cin) { return (long long)(((
 extern "C" int tsr_pack_conv_weight_pair_f16s(const float* w3_oihw, const float* w5_oihw, void* w_packed, int cin,
                                               float wscale, const float* w_amax, void* stream) {
   if (!w3_oihw || !w5_oihw || !w_packed || cin <= 0 || (cin & 15) || (!w_amax && !(wscale > 0.f))) return TSR_ERR_ARG;
-  const size_t total = (size_t)128 * ((cin + 31) & ~31) * 25;
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_pair_kernel, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0, (hipStream_t)stream, w3_oihw,
-                     w5_oihw, (_Float16*)w_packed, cin, wscale, w_amax);
+  hipLaunchKernelGGL(pack_pair_kernel, pack_grid((size_t)128 * ((cin + 31) & ~31) * 25), dim3(256), 0, (hipStream_t)stream,
+                     w3_oihw, w5_oihw, (_Float16*)w_packed, cin, wscale, w_amax);
   return tsr_check_launch();
 }
 
@@ -633,16 +627,10 @@ extern "C" int tsr_conv2d_fwd_f16s_pair(const float* in, int in_ctot, int in_cof
                                         float w_inv_scale, const float* in_amax, float* out_amax,
                                         const float* scale, const float* shift, float* out, int out_ctot, int out_coff,
                                         int relu, int B, int H, int W, void* stream) {
-  if (!in || !w_packed || !out || !in_amax || B <= 0 || H <= 0 || W <= 0 || !(w_inv_scale > 0.f)) return TSR_ERR_ARG;
-  if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + 128 > out_ctot)
+  ConvArgs a;
+  if (!f16s_scales_ok(in_amax, w_inv_scale) ||
+      conv_fill(a, in, in_ctot, in_coff, cin, w_packed, scale, shift, nullptr, 0, 0, out, out_ctot, out_coff, 128, relu, B, H, W))
     return TSR_ERR_ARG;
-  ConvArgs a = {};
-  a.in = in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
-  a.wp = (const float*)w_packed; a.scale = scale; a.shift = shift;
-  a.out = out; a.out_ctot = out_ctot; a.out_coff = out_coff; a.relu = relu;
-  a.B = B; a.H = H; a.W = W;
-  a.tiles_x = (W + 7) / 8; a.tiles_y = (H + 7) / 8;
   a.in_amax = in_amax; a.w_inv_scale = w_inv_scale; a.out_amax = out_amax;
   const int grid = ((B + 1) / 2) * a.tiles_x * a.tiles_y;
   hipLaunchKernelGGL((conv_k32_kernel<5, 128, false, 2, false, false, 256, true>), dim3(grid), dim3(256), 0,

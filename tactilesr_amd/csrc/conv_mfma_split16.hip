@@ -24,6 +24,7 @@
 #include "conv_args.h"
 #include "conv_epilogue.h"
 #include "conv_fuse1x1.h"
+#include "conv_host.h"
 #include "tactilesr_hip.h"
 #include <type_traits>
 
@@ -516,8 +517,6 @@ __global__ void pack_conv_weight_bf16s_kernel(const float* __restrict__ w, typen
 
 // fp16x3 3x3 / 5x5 convolutions run on conv_mfma_k32.hip (16x16x32 MFMA, tap pairs); the 1x1 layers and the other
 // arithmetic modes stay on the 32x32x16 kernel of this file.  Pack and launch ask the same question (use_k32).
-int tsr_conv_k32(const ConvArgs& a, int cout, int ks, bool ext, hipStream_t st);      // conv_mfma_k32.hip
-int tsr_conv_k32_fuse1x1(const ConvArgs& a, int ks, hipStream_t st);
 // C_out = 64 convs run the K = 32 kernel too since round 3 (4 images x all 64 channels per workgroup): 3x3 eval 1.62 ->
 // 1.46 ms per launch at B = 4096, train (B = 2048) 3x3 dgrad 1.02 -> 0.96 ms, 5x5 forward 1.61 -> 1.45, 5x5 dgrad
 // 1.74 -> 1.63.  In round 2 the training instantiation of the 5x5 form ran 3x slower: one of the kernel's lambdas was
@@ -528,7 +527,6 @@ static bool use_k32(int ks, int kdim, int cout) {
   return ks > 1 && (cout == 128 || cout == 64);
 }
 // images per workgroup (= statistics-slab entries per workgroup) of the fp16x3 kernel that runs (cout, ks)
-int tsr_conv_k32_images(int cout);            // conv_mfma_k32.hip
 int tsr_conv_f16s_images(int cout, int ks) {
   if (use_k32(ks, 0, cout)) return tsr_conv_k32_images(cout);
   return (ks > 1 && cout == 64) ? 4 : 2;
@@ -544,73 +542,58 @@ extern "C" long long tsr_conv_weight_bf16s_elems(int cout, int cin, int ks, int 
   return a > b ? a : b;
 }
 
+// The one launch of pack_conv_weight_bf16s_kernel.  Forward pack: (cout, cin) of the conv, ci0 = -1.  dgrad pack: cout :=
+// nprime, cin := the forward conv's C_out, ci0 >= 0 and cin_f = the forward conv's C_in.  F16: two fp16 planes of w * wscale
+// (or of w * the power of two derived from *w_amax) in the order of the kernel that runs the shape (k32_mode); else `ns`
+// bf16 planes.
+template <bool F16>
+static int pack_bf16s(const float* w, void* wp, int cout, int cin, int ks, int ns, int ci0, int cin_f, float wscale,
+                      const float* w_amax, void* stream) {
+  const int k32 = F16 ? k32_mode(ks, cin, cout) : 0;
+  const int tps = k32 ? 1 : taps_per_step(ks, cout, ns);
+  const size_t total = (size_t)cout * cin * (((ks * ks + tps - 1) / tps) * tps);
+  hipLaunchKernelGGL(pack_conv_weight_bf16s_kernel<F16>, pack_grid(total), dim3(256), 0, (hipStream_t)stream, w,
+                     (typename Plane<F16>::T*)wp, cout, cin, ks, ns, tps, ci0, cin_f, wscale, w_amax, k32);
+  return tsr_check_launch();
+}
+
 extern "C" int tsr_pack_conv_weight_bf16s(const float* w_oihw, void* w_packed, int cout, int cin, int ks,
                                           int nsplit, void* stream) {
-  if (!w_oihw || !w_packed || cin <= 0 || (cin & 15) || (cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5) ||
-      nsplit < 1 || nsplit > 3)
-    return TSR_ERR_ARG;
-  const int tps = taps_per_step(ks, cout, nsplit);
-  const size_t total = (size_t)cout * cin * (((ks * ks + tps - 1) / tps) * tps);
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_conv_weight_bf16s_kernel<false>, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0,
-                     (hipStream_t)stream, w_oihw, (__bf16*)w_packed, cout, cin, ks, nsplit, tps, -1, 0, 1.0f, nullptr, 0);
-  return tsr_check_launch();
+  if (!w_oihw || !w_packed || !pack_shape_ok(cout, cin, ks) || nsplit < 1 || nsplit > 3) return TSR_ERR_ARG;
+  return pack_bf16s<false>(w_oihw, w_packed, cout, cin, ks, nsplit, -1, 0, 1.0f, nullptr, stream);
 }
 
 // fp16 two-plane packing: planes of w*wscale (wscale a power of two chosen by the caller so that
 // max|w|*wscale lies in [2^13, 2^14)); tsr_conv2d_fwd_f16s gets 1/wscale back.
 extern "C" int tsr_pack_conv_weight_f16s(const float* w_oihw, void* w_packed, int cout, int cin, int ks,
                                          float wscale, void* stream) {
-  if (!w_oihw || !w_packed || cin <= 0 || (cin & 15) || (cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5) ||
-      !(wscale > 0.f))
-    return TSR_ERR_ARG;
-  const int k32 = k32_mode(ks, cin, cout);
-  const int tps = k32 ? 1 : taps_per_step(ks, cout, 2);
-  const size_t total = (size_t)cout * cin * (((ks * ks + tps - 1) / tps) * tps);
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_conv_weight_bf16s_kernel<true>, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0,
-                     (hipStream_t)stream, w_oihw, (_Float16*)w_packed, cout, cin, ks, 2, tps, -1, 0, wscale, nullptr, k32);
-  return tsr_check_launch();
+  if (!w_oihw || !w_packed || !pack_shape_ok(cout, cin, ks) || !(wscale > 0.f)) return TSR_ERR_ARG;
+  return pack_bf16s<true>(w_oihw, w_packed, cout, cin, ks, 2, -1, 0, wscale, nullptr, stream);
 }
 
 extern "C" int tsr_pack_conv_weight_f16s_dev(const float* w_oihw, void* w_packed, int cout, int cin, int ks,
                                              const float* w_amax, void* stream) {
-  if (!w_oihw || !w_packed || !w_amax || cin <= 0 || (cin & 15) || (cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5))
-    return TSR_ERR_ARG;
-  const int k32 = k32_mode(ks, cin, cout);
-  const int tps = k32 ? 1 : taps_per_step(ks, cout, 2);
-  const size_t total = (size_t)cout * cin * (((ks * ks + tps - 1) / tps) * tps);
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_conv_weight_bf16s_kernel<true>, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0,
-                     (hipStream_t)stream, w_oihw, (_Float16*)w_packed, cout, cin, ks, 2, tps, -1, 0, 1.0f, w_amax, k32);
-  return tsr_check_launch();
+  if (!w_oihw || !w_packed || !w_amax || !pack_shape_ok(cout, cin, ks)) return TSR_ERR_ARG;
+  return pack_bf16s<true>(w_oihw, w_packed, cout, cin, ks, 2, -1, 0, 1.0f, w_amax, stream);
 }
 
 extern "C" int tsr_pack_conv_weight_dgrad_f16s_dev(const float* w_oihw, void* w_packed, int cout, int cin, int ks,
                                                    int ci0, int nprime, const float* w_amax, void* stream) {
-  if (!w_oihw || !w_packed || !w_amax || (cout & 15) || (nprime != 64 && nprime != 128) || ci0 < 0 ||
-      ci0 + nprime > cin || (ks != 1 && ks != 3 && ks != 5))
-    return TSR_ERR_ARG;
-  const int k32 = k32_mode(ks, cout, nprime);
-  const int tps = k32 ? 1 : taps_per_step(ks, nprime, 2);
-  const size_t total = (size_t)nprime * cout * (((ks * ks + tps - 1) / tps) * tps);
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_conv_weight_bf16s_kernel<true>, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0,
-                     (hipStream_t)stream, w_oihw, (_Float16*)w_packed, nprime, cout, ks, 2, tps, ci0, cin, 1.0f, w_amax, k32);
-  return tsr_check_launch();
+  if (!w_oihw || !w_packed || !w_amax || !pack_dgrad_shape_ok(cout, cin, ks, ci0, nprime)) return TSR_ERR_ARG;
+  return pack_bf16s<true>(w_oihw, w_packed, nprime, cout, ks, 2, ci0, cin, 1.0f, w_amax, stream);
 }
 
 extern "C" int tsr_pack_conv_weight_dgrad_bf16s(const float* w_oihw, void* w_packed, int cout, int cin, int ks,
                                                 int ci0, int nprime, int nsplit, void* stream) {
-  if (!w_oihw || !w_packed || (cout & 15) || (nprime != 64 && nprime != 128) || ci0 < 0 || ci0 + nprime > cin ||
-      (ks != 1 && ks != 3 && ks != 5) || nsplit < 1 || nsplit > 3)
+  if (!w_oihw || !w_packed || !pack_dgrad_shape_ok(cout, cin, ks, ci0, nprime) || nsplit < 1 || nsplit > 3)
     return TSR_ERR_ARG;
-  const int tps = taps_per_step(ks, nprime, nsplit);
-  const size_t total = (size_t)nprime * cout * (((ks * ks + tps - 1) / tps) * tps);
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_conv_weight_bf16s_kernel<false>, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0,
-                     (hipStream_t)stream, w_oihw, (__bf16*)w_packed, nprime, cout, ks, nsplit, tps, ci0, cin, 1.0f, nullptr, 0);
-  return tsr_check_launch();
+  return pack_bf16s<false>(w_oihw, w_packed, nprime, cout, ks, nsplit, ci0, cin, 1.0f, nullptr, stream);
+}
+
+extern "C" int tsr_pack_conv_weight_dgrad_f16s(const float* w_oihw, void* w_packed, int cout, int cin, int ks,
+                                               int ci0, int nprime, float wscale, void* stream) {
+  if (!w_oihw || !w_packed || !pack_dgrad_shape_ok(cout, cin, ks, ci0, nprime) || !(wscale > 0.f)) return TSR_ERR_ARG;
+  return pack_bf16s<true>(w_oihw, w_packed, nprime, cout, ks, 2, ci0, cin, wscale, nullptr, stream);
 }
 
 template <int KS, int COUT, int NS, bool EXT, bool F16>
@@ -638,30 +621,8 @@ static int launch_bf16s(const ConvArgs& a, hipStream_t st) {
 
 template <int NS, bool EXT, bool F16 = false>
 static int dispatch_bf16s(const ConvArgs& a, int cout, int ks, hipStream_t st) {
-  if (cout == 64) {
-    if (ks == 1) return launch_bf16s<1, 64, NS, EXT, F16>(a, st);
-    if (ks == 3) return launch_bf16s<3, 64, NS, EXT, F16>(a, st);
-    if (ks == 5) return launch_bf16s<5, 64, NS, EXT, F16>(a, st);
-  } else if (cout == 128) {
-    if (ks == 1) return launch_bf16s<1, 128, NS, EXT, F16>(a, st);
-    if (ks == 3) return launch_bf16s<3, 128, NS, EXT, F16>(a, st);
-    if (ks == 5) return launch_bf16s<5, 128, NS, EXT, F16>(a, st);
-  }
-  return TSR_ERR_ARG;
-}
-
-extern "C" int tsr_pack_conv_weight_dgrad_f16s(const float* w_oihw, void* w_packed, int cout, int cin, int ks,
-                                               int ci0, int nprime, float wscale, void* stream) {
-  if (!w_oihw || !w_packed || (cout & 15) || (nprime != 64 && nprime != 128) || ci0 < 0 || ci0 + nprime > cin ||
-      (ks != 1 && ks != 3 && ks != 5) || !(wscale > 0.f))
-    return TSR_ERR_ARG;
-  const int k32 = k32_mode(ks, cout, nprime);
-  const int tps = k32 ? 1 : taps_per_step(ks, nprime, 2);
-  const size_t total = (size_t)nprime * cout * (((ks * ks + tps - 1) / tps) * tps);
-  const int grid = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_conv_weight_bf16s_kernel<true>, dim3(grid > 4096 ? 4096 : grid), dim3(256), 0,
-                     (hipStream_t)stream, w_oihw, (_Float16*)w_packed, nprime, cout, ks, 2, tps, ci0, cin, wscale, nullptr, k32);
-  return tsr_check_launch();
+  return for_cout_ks(cout, ks,
+                     [&](auto CO, auto KS) { return launch_bf16s<decltype(KS)::value, decltype(CO)::value, NS, EXT, F16>(a, st); });
 }
 
 // 1x1 convolution on bf16 CB16 tensors as a STREAMING GEMM (training with bf16 activation storage: the MSRB `confusion`
@@ -784,18 +745,8 @@ static int launch_b16_ex(const ConvArgs& a, hipStream_t st) {
   return tsr_check_launch();
 }
 
-int tsr_conv_b16k_ex(const ConvArgs& a, int cout, int ks, bool pair, hipStream_t st);       // conv_b16k.hip
 static int dispatch_b16_ex(const ConvArgs& a, int cout, int ks, hipStream_t st) {
-  if (cout == 64) {
-    if (ks == 1) return launch_b16_ex<1, 64>(a, st);
-    if (ks == 3) return launch_b16_ex<3, 64>(a, st);
-    if (ks == 5) return launch_b16_ex<5, 64>(a, st);
-  } else if (cout == 128) {
-    if (ks == 1) return launch_b16_ex<1, 128>(a, st);
-    if (ks == 3) return launch_b16_ex<3, 128>(a, st);
-    if (ks == 5) return launch_b16_ex<5, 128>(a, st);
-  }
-  return TSR_ERR_ARG;
+  return for_cout_ks(cout, ks, [&](auto CO, auto KS) { return launch_b16_ex<decltype(KS)::value, decltype(CO)::value>(a, st); });
 }
 
 // tsr_conv2d_ex with nsplit != 0 lands here (argument checks were done by the caller)
@@ -815,18 +766,10 @@ extern "C" int tsr_conv2d_fwd_bf16s(const float* in, int in_ctot, int in_coff, i
                                     const float* res, int res_ctot, int res_coff,
                                     float* out, int out_ctot, int out_coff, int relu,
                                     int B, int H, int W, void* stream) {
-  if (!in || !w_packed || !out || B <= 0 || H <= 0 || W <= 0 || nsplit < 1 || nsplit > 3) return TSR_ERR_ARG;
-  if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + cout > out_ctot)
+  ConvArgs a;
+  if (nsplit < 1 || nsplit > 3 || conv_fill(a, in, in_ctot, in_coff, cin, w_packed, scale, shift, res, res_ctot, res_coff, out,
+                                            out_ctot, out_coff, cout, relu, B, H, W))
     return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
-  ConvArgs a = {};
-  a.in = in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
-  a.wp = (const float*)w_packed; a.scale = scale; a.shift = shift;
-  a.res = res; a.res_ctot = res_ctot; a.res_coff = res_coff;
-  a.out = out; a.out_ctot = out_ctot; a.out_coff = out_coff; a.relu = relu;
-  a.B = B; a.H = H; a.W = W;
-  a.tiles_x = (W + 7) / 8; a.tiles_y = (H + 7) / 8;
   hipStream_t st = (hipStream_t)stream;
   if (nsplit == 3) return dispatch_bf16s<3, false>(a, cout, ks, st);
   if (nsplit == 2) return dispatch_bf16s<2, false>(a, cout, ks, st);
@@ -843,20 +786,11 @@ extern "C" int tsr_conv2d_fwd_f16s_fuse1x1(const float* in, int in_ctot, int in_
                                            const float* res, int res_ctot, int res_coff,
                                            float* out, int out_ctot, int out_coff, int relu2,
                                            int B, int H, int W, void* stream) {
-  if (!in || !w_packed || !w2_packed || !out || !in_amax || B <= 0 || H <= 0 || W <= 0 || !(w_inv_scale > 0.f) ||
-      !(w2_inv_scale > 0.f) || (ks != 3 && ks != 5))
+  ConvArgs a;
+  if (!f16s_scales_ok(in_amax, w_inv_scale) || !w2_packed || !(w2_inv_scale > 0.f) || (ks != 3 && ks != 5) ||
+      conv_fill(a, in, in_ctot, in_coff, cin, w_packed, scale, shift, res, res_ctot, res_coff, out, out_ctot, out_coff, 64, relu,
+                B, H, W))
     return TSR_ERR_ARG;
-  if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + 64 > out_ctot)
-    return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + 64 > res_ctot)) return TSR_ERR_ARG;
-  ConvArgs a = {};
-  a.in = in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
-  a.wp = (const float*)w_packed; a.scale = scale; a.shift = shift; a.relu = relu;
-  a.res = res; a.res_ctot = res_ctot; a.res_coff = res_coff;
-  a.out = out; a.out_ctot = out_ctot; a.out_coff = out_coff;
-  a.B = B; a.H = H; a.W = W;
-  a.tiles_x = (W + 7) / 8; a.tiles_y = (H + 7) / 8;
   a.in_amax = in_amax; a.w_inv_scale = w_inv_scale; a.out_amax = out_amax;
   a.w2 = w2_packed; a.w2_inv_scale = w2_inv_scale; a.shift2 = shift2; a.relu2 = relu2;
   const int grid = ((B + 1) / 2) * a.tiles_x * a.tiles_y;
@@ -898,30 +832,12 @@ extern "C" int tsr_conv2d_fwd_b16(const void* in, int in_ctot, int in_coff, int 
                                   const void* res, int res_ctot, int res_coff,
                                   void* out, int out_ctot, int out_coff, int relu,
                                   int B, int H, int W, void* stream) {
-  if (!in || !w_packed || !out || B <= 0 || H <= 0 || W <= 0) return TSR_ERR_ARG;
-  if ((cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5)) return TSR_ERR_ARG;
-  if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + cout > out_ctot)
+  ConvArgs a;
+  if (conv_fill(a, in, in_ctot, in_coff, cin, w_packed, scale, shift, res, res_ctot, res_coff, out, out_ctot, out_coff, cout,
+                relu, B, H, W))
     return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
-  ConvArgs a = {};
-  a.in = (const float*)in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
-  a.wp = (const float*)w_packed; a.scale = scale; a.shift = shift;
-  a.res = (const float*)res; a.res_ctot = res_ctot; a.res_coff = res_coff;
-  a.out = (float*)out; a.out_ctot = out_ctot; a.out_coff = out_coff; a.relu = relu;
-  a.B = B; a.H = H; a.W = W;
-  a.tiles_x = (W + 7) / 8; a.tiles_y = (H + 7) / 8;
   hipStream_t st = (hipStream_t)stream;
-  if (cout == 64) {
-    if (ks == 1) return launch_b16<1, 64>(a, st);
-    if (ks == 3) return launch_b16<3, 64>(a, st);
-    if (ks == 5) return launch_b16<5, 64>(a, st);
-  } else if (cout == 128) {
-    if (ks == 1) return launch_b16<1, 128>(a, st);
-    if (ks == 3) return launch_b16<3, 128>(a, st);
-    if (ks == 5) return launch_b16<5, 128>(a, st);
-  }
-  return TSR_ERR_ARG;
+  return for_cout_ks(cout, ks, [&](auto CO, auto KS) { return launch_b16<decltype(KS)::value, decltype(CO)::value>(a, st); });
 }
 
 // fp16 two-plane variant ("fp16x3": x*sx = h1+h2, w*sw = g1+g2, products h1g1 + h1g2 + h2g1, fp32 accumulate).
@@ -934,19 +850,11 @@ extern "C" int tsr_conv2d_fwd_f16s(const float* in, int in_ctot, int in_coff, in
                                    const float* res, int res_ctot, int res_coff,
                                    float* out, int out_ctot, int out_coff, int relu,
                                    int B, int H, int W, void* stream) {
-  if (!in || !w_packed || !out || !in_amax || B <= 0 || H <= 0 || W <= 0 || !(w_inv_scale > 0.f)) return TSR_ERR_ARG;
-  if ((cout != 64 && cout != 128) || (ks != 1 && ks != 3 && ks != 5)) return TSR_ERR_ARG;
-  if ((cin & 15) || (in_ctot & 15) || (in_coff & 15) || (out_ctot & 15) || (out_coff & 15) || cin <= 0 ||
-      in_coff < 0 || out_coff < 0 || in_coff + cin > in_ctot || out_coff + cout > out_ctot)
+  ConvArgs a;
+  if (!f16s_scales_ok(in_amax, w_inv_scale) ||
+      conv_fill(a, in, in_ctot, in_coff, cin, w_packed, scale, shift, res, res_ctot, res_coff, out, out_ctot, out_coff, cout,
+                relu, B, H, W))
     return TSR_ERR_ARG;
-  if (res && ((res_ctot & 15) || (res_coff & 15) || res_coff < 0 || res_coff + cout > res_ctot)) return TSR_ERR_ARG;
-  ConvArgs a = {};
-  a.in = in; a.in_ctot = in_ctot; a.in_coff = in_coff; a.cin = cin;
-  a.wp = (const float*)w_packed; a.scale = scale; a.shift = shift;
-  a.res = res; a.res_ctot = res_ctot; a.res_coff = res_coff;
-  a.out = out; a.out_ctot = out_ctot; a.out_coff = out_coff; a.relu = relu;
-  a.B = B; a.H = H; a.W = W;
-  a.tiles_x = (W + 7) / 8; a.tiles_y = (H + 7) / 8;
   a.in_amax = in_amax; a.w_inv_scale = w_inv_scale; a.out_amax = out_amax;
   return dispatch_bf16s<2, false, true>(a, cout, ks, (hipStream_t)stream);
 }

@@ -30,7 +30,7 @@
 //     shared with the forward convolutions of the same stage.
 #include "tsr_common.h"
 #include "tactilesr_hip.h"
-#include <type_traits>
+#include "conv_host.h"
 
 typedef __bf16 gb16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 gb16x4 __attribute__((ext_vector_type(4)));

@@ -22,7 +22,7 @@
 // apart (pixel counts padded to 4 mod 8), i.e. complementary halves of the 64-bank row for ANY start pixel: conflict
 // free for every tap.  Staging writes are 8 B per lane, 512 contiguous bytes per wave: conflict free.
 #include "tsr_common.h"
-#include <type_traits>
+#include "conv_host.h"
 
 typedef __bf16 tb16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 tb16x4 __attribute__((ext_vector_type(4)));
@@ -852,8 +852,6 @@ static int launch_tr16(const WgradTArgs& g, hipStream_t st) {
   }
 }
 
-int tsr_wgrad_b16k_1x1_wgs(int cout, int cin);          // wgrad_b16k.hip
-
 template <int KS> static int tr16_wgs(int cout, int cin, int planes) {
   if (planes == 3) {
     typedef WgradTCfg<KS, 3> C;
@@ -884,12 +882,7 @@ extern "C" int tsr_conv2d_wgrad_splits(int cout, int cin, int ks, int planes, in
   return (int)ns;
 }
 
-bool tsr_wgrad_b16k_ok(int cout, int cin, int ks, int H, int W, int a_ctot, int dz_ctot);            // wgrad_b16k.hip
-int tsr_wgrad_b16k(const void* a, int a_ctot, int a_coff, int cin, const float* a_scale, const float* a_shift, const void* dz,
-                   int dz_ctot, int dz_coff, int cout, int ks, float* slab, float* bias_slab, int nsplit, int B, int H, int W,
-                   hipStream_t st);
-
-int tsr_conv2d_wgrad_tr16(const float* a, int a_ctot, int a_coff, int cin, const float* a_scale, const float* a_shift,
+static int tsr_conv2d_wgrad_tr16(const float* a, int a_ctot, int a_coff, int cin, const float* a_scale, const float* a_shift,
                           const float* dz, int dz_ctot, int dz_coff, int cout, int ks, int planes,
                           const float* a_amax, const float* dz_amax, float* slab, float* bias_slab, int nsplit,
                           int B, int H, int W, hipStream_t st) {

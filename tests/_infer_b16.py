@@ -139,7 +139,7 @@ TABLES = {"b16": B16_CASES, "b16k": B16K_CASES, "pair": PAIR_CASES, "fuse1x1": F
 
 # ---------------------------------------------------------------------------------------------------- launch geometry
 def images_per_workgroup(kind, ks=3):
-    """launch_b16 (csrc/conv_mfma_split16.hip): 4 for 3x3 / 5x5, 2 for 1x1; B16K_LAUNCH (csrc/conv_b16k.hip): TSR_B16K_NW."""
+    """launch_b16 (csrc/conv_mfma_split16.hip): 4 for 3x3 / 5x5, 2 for 1x1; b16k_launch (csrc/conv_b16k.hip): TSR_B16K_NW."""
     return 2 if kind == "b16" and ks == 1 else 4
 
 

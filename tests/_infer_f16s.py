@@ -1,6 +1,8 @@
 """Case tables, layouts, fp64 references and the per-image checker of tests/test_gpu_infer_fp16x3.py -- everything that runs
 without a GPU (tests/test_infer_f16s_cpu.py checks the references, the checker and the tables), plus the pack calls of the
-fp16x3 inference launches (`tactilesr_amd._lib` is imported inside them, never at module level).
+fp16x3 inference launches (`tactilesr_amd._lib` is imported inside them, never at module level), and the REFUSAL TABLES of the
+three launches and of the pack routines (the end of this file): the GPU test sends them to real buffers and checks that a
+refused call wrote nothing, the CPU test sends them with fake pointers and checks the status alone.
 
 The launches under test are the INFERENCE instantiations (`EXT = false`) behind `conv_impl = "fp16x3"`:
 
@@ -366,3 +368,127 @@ def pack_pair(w3, w5, dev=False):
 def pack_w2(w2):
     """The 64x128 1x1 half of `confusion` for tsr_conv2d_fwd_f16s_fuse1x1: tsr_pack_conv_weight_f16s of [64][128][1][1]."""
     return pack_f16s(w2.reshape(64, 128, 1, 1))
+
+
+# ---------------------------------------------------------------------------------------------------- refusals
+# Argument lists (name:type, p = pointer, i = int, f = float; the stream comes last) of the entry points under test.
+F16S_SIG = ["in:p", "in_ctot:i", "in_coff:i", "cin:i", "w_packed:p", "cout:i", "ks:i", "w_inv_scale:f", "in_amax:p", "out_amax:p",
+            "scale:p", "shift:p", "res:p", "res_ctot:i", "res_coff:i", "out:p", "out_ctot:i", "out_coff:i", "relu:i", "B:i", "H:i", "W:i"]
+PAIR_SIG = ["in:p", "in_ctot:i", "in_coff:i", "cin:i", "w_packed:p", "w_inv_scale:f", "in_amax:p", "out_amax:p", "scale:p", "shift:p",
+            "out:p", "out_ctot:i", "out_coff:i", "relu:i", "B:i", "H:i", "W:i"]
+FUSE_SIG = ["in:p", "in_ctot:i", "in_coff:i", "cin:i", "w_packed:p", "ks:i", "w_inv_scale:f", "in_amax:p", "out_amax:p", "scale:p",
+            "shift:p", "relu:i", "w2_packed:p", "w2_inv_scale:f", "shift2:p", "res:p", "res_ctot:i", "res_coff:i", "out:p",
+            "out_ctot:i", "out_coff:i", "relu2:i", "B:i", "H:i", "W:i"]
+PACK_SIG = ["w:p", "w_packed:p", "cout:i", "cin:i", "ks:i", "wscale:f"]
+PACK_DEV_SIG = ["w:p", "w_packed:p", "cout:i", "cin:i", "ks:i", "w_amax:p"]
+PACK_PAIR_SIG = ["w3:p", "w5:p", "w_packed:p", "cin:i", "wscale:f", "w_amax:p"]
+_DGRAD = ["w:p", "w_packed:p", "cout:i", "cin:i", "ks:i", "ci0:i", "nprime:i"]
+DGRAD_PACK_SIGS = {
+    "tsr_pack_conv_weight_dgrad": _DGRAD,
+    "tsr_pack_conv_weight_dgrad_bf16s": _DGRAD + ["nsplit:i"],
+    "tsr_pack_conv_weight_dgrad_f16s": _DGRAD + ["wscale:f"],
+    "tsr_pack_conv_weight_dgrad_f16s_dev": _DGRAD + ["w_amax:p"],
+    "tsr_pack_conv_weight_dgrad_b16k": _DGRAD,
+}
+LAUNCHES = {"f16s": ("tsr_conv2d_fwd_f16s", F16S_SIG), "pair": ("tsr_conv2d_fwd_f16s_pair", PAIR_SIG),
+            "fuse1x1": ("tsr_conv2d_fwd_f16s_fuse1x1", FUSE_SIG)}
+FAKE = 16                               # a non-NULL pointer value that is never dereferenced (the CPU test's)
+BAD_SCALES = [0.0, -1.0, NAN]
+
+# The valid argument list every launch's refusal test starts from: B = 1, a 5x3 image, one channel block in.
+REFUSAL_CASES = {"f16s": F16sCase(3, 16, 64, 1, 5, 3, True, True, True, 1, "zero", (16, 32, 48)),
+                 "pair": PairCase(16, 1, 5, 3, True, True, 1, "zero", (16, 32)),
+                 "fuse1x1": FuseCase(3, 16, 1, 5, 3, 1, True, True, True, True, 1, "zero", (16, 32, 48))}
+REFUSAL_WIDTH = {"f16s": 64, "pair": 128, "fuse1x1": 64}          # channels of `out` (and `res`)
+
+
+def slice_mutations(cin, cout, with_res=True):
+    """Overrides that make a slice description invalid: not a multiple of 16, or leaving its buffer on either side."""
+    m = [{"cin": cin + 8}, {"cin": 0}, {"cin": -16}, {"in_ctot": cin + PAD - 8}, {"in_coff": 8}, {"out_ctot": cout + PAD - 8},
+         {"out_coff": 24}, {"in_coff": PAD + 16}, {"in_coff": -16}, {"out_coff": PAD + 16}, {"out_coff": -16},
+         {"in_ctot": cin - 16, "in_coff": 0}, {"out_ctot": cout - 16, "out_coff": 0}]
+    if with_res:
+        m += [{"res_ctot": cout + PAD - 8}, {"res_coff": 8}, {"res_coff": PAD + 16}, {"res_coff": -16},
+              {"res_ctot": cout - 16, "res_coff": 0}]
+    return m
+
+
+def common_mutations(required):
+    return ([{k: None} for k in required] + [{d: v} for d in ("B", "H", "W") for v in (0, -1)]
+            + [{"w_inv_scale": v} for v in BAD_SCALES])
+
+
+def launch_mutations(kind):
+    """Every argument list the launch of `kind` must refuse with status 1, as overrides of its valid list."""
+    if kind == "f16s":
+        return (common_mutations(["in", "w_packed", "out", "in_amax"]) + slice_mutations(16, 64)
+                + [{"cout": v} for v in (0, 32, 96, 256)] + [{"ks": v} for v in (-3, 0, 2, 4, 7)])
+    if kind == "pair":
+        return common_mutations(["in", "w_packed", "out", "in_amax"]) + slice_mutations(16, 128, with_res=False)
+    return (common_mutations(["in", "w_packed", "out", "in_amax", "w2_packed"]) + slice_mutations(16, 64)
+            + [{"w2_inv_scale": v} for v in BAD_SCALES] + [{"ks": v} for v in (-3, 0, 1, 2, 4, 7)])
+
+
+def fake_launch_args(kind):
+    """The valid list of `kind` with fake pointers everywhere (the integers are those of the GPU test's list)."""
+    c = REFUSAL_CASES[kind]
+    width = REFUSAL_WIDTH[kind]
+    v = {"in_ctot": c.cin + PAD, "in_coff": c.offs[0], "cin": c.cin, "out_ctot": width + PAD, "out_coff": c.offs[1], "relu": c.relu,
+         "B": c.B, "H": c.H, "W": c.W, "w_inv_scale": 2.0 ** -14, "w2_inv_scale": 2.0 ** -14, "relu2": 1}
+    if kind != "pair":
+        v.update(res_ctot=width + PAD, res_coff=c.offs[2], ks=c.ks)
+    if kind == "f16s":
+        v.update(cout=c.cout)
+    v.update({s.split(":")[0]: FAKE for s in LAUNCHES[kind][1] if s.endswith(":p")})
+    return v
+
+
+# the pack routines: (cout, cin, ks) of the valid lists (the last is fuse1x1's 1x1 half), the pair pack's cin
+PACK_SHAPES = [(64, 16, 3), (128, 32, 5), (64, 128, 1)]
+PACK_PAIR_CIN = 32
+
+
+def pack_shape_mutations(cin):
+    return [{"cin": cin + 8}, {"cin": 0}, {"cin": -16}, {"cout": 0}, {"cout": 32}, {"cout": 96}, {"cout": 256},
+            {"ks": -3}, {"ks": 0}, {"ks": 2}, {"ks": 4}, {"ks": 7}, {"w": None}, {"w_packed": None}]
+
+
+def pack_host_mutations(cin):
+    """tsr_pack_conv_weight_f16s"""
+    return pack_shape_mutations(cin) + [{"wscale": v} for v in BAD_SCALES]
+
+
+def pack_dev_mutations(cin):
+    """tsr_pack_conv_weight_f16s_dev"""
+    return pack_shape_mutations(cin) + [{"w_amax": None}]
+
+
+def pack_pair_mutations(cin):
+    """tsr_pack_conv_weight_pair_f16s (valid list: wscale > 0, w_amax NULL)"""
+    return ([{"w3": None}, {"w5": None}, {"w_packed": None}, {"cin": cin + 8}, {"cin": 0}, {"cin": -16}]
+            + [{"wscale": v} for v in BAD_SCALES])
+
+
+# dgrad packs: the gradient of input channels [ci0, ci0 + nprime) of a conv with OIHW weight [cout][cin][ks][ks]
+DGRAD_PACK_VALID = {"cout": 64, "cin": 192, "ks": 3, "ci0": 64, "nprime": 128, "nsplit": 3, "wscale": 2.0 ** 14}
+
+
+def dgrad_pack_mutations(name):
+    m = [{"w": None}, {"w_packed": None}, {"cout": 72}, {"cout": 8}, {"nprime": 0}, {"nprime": 32}, {"nprime": 96}, {"nprime": 256},
+         {"ci0": -16}, {"ci0": -128}, {"ci0": 80}, {"ci0": 192}, {"cin": 128}, {"ks": -3}, {"ks": 0}, {"ks": 2}, {"ks": 4}, {"ks": 7}]
+    if name.endswith("_dev"):
+        m.append({"w_amax": None})
+    return m
+
+
+def raw_fake(name, sig, vals):
+    """Status of entry point `name` for `vals` (name -> None / fake pointer value / int / float), NULL stream: never reaches
+    a device unless every check passes (then, without a device, the launch fails with status 2)."""
+    import ctypes
+    from tactilesr_amd import _lib
+    args = []
+    for s in sig:
+        n, t = s.split(":")
+        v = vals[n]
+        args.append(ctypes.c_void_p(v or 0) if t == "p" else (ctypes.c_int(v) if t == "i" else ctypes.c_float(v)))
+    return getattr(_lib.load(), name)(*args, ctypes.c_void_p(0))

@@ -32,7 +32,7 @@ import pytest
 import torch
 
 import _infer_f16s as S
-from _infer_f16s import PAD, TOL, NAN
+from _infer_f16s import PAD, TOL, F16S_SIG, PAIR_SIG, FUSE_SIG, PACK_SIG, PACK_DEV_SIG, PACK_PAIR_SIG
 
 pytestmark = pytest.mark.gpu
 
@@ -54,18 +54,6 @@ def f32(v):
 
 
 # ---------------------------------------------------------------------------------------------------------------- launches
-F16S_SIG = ["in:p", "in_ctot:i", "in_coff:i", "cin:i", "w_packed:p", "cout:i", "ks:i", "w_inv_scale:f", "in_amax:p", "out_amax:p",
-            "scale:p", "shift:p", "res:p", "res_ctot:i", "res_coff:i", "out:p", "out_ctot:i", "out_coff:i", "relu:i", "B:i", "H:i", "W:i"]
-PAIR_SIG = ["in:p", "in_ctot:i", "in_coff:i", "cin:i", "w_packed:p", "w_inv_scale:f", "in_amax:p", "out_amax:p", "scale:p", "shift:p",
-            "out:p", "out_ctot:i", "out_coff:i", "relu:i", "B:i", "H:i", "W:i"]
-FUSE_SIG = ["in:p", "in_ctot:i", "in_coff:i", "cin:i", "w_packed:p", "ks:i", "w_inv_scale:f", "in_amax:p", "out_amax:p", "scale:p",
-            "shift:p", "relu:i", "w2_packed:p", "w2_inv_scale:f", "shift2:p", "res:p", "res_ctot:i", "res_coff:i", "out:p",
-            "out_ctot:i", "out_coff:i", "relu2:i", "B:i", "H:i", "W:i"]
-PACK_SIG = ["w:p", "w_packed:p", "cout:i", "cin:i", "ks:i", "wscale:f"]
-PACK_DEV_SIG = ["w:p", "w_packed:p", "cout:i", "cin:i", "ks:i", "w_amax:p"]
-PACK_PAIR_SIG = ["w3:p", "w5:p", "w_packed:p", "cin:i", "wscale:f", "w_amax:p"]
-
-
 def raw(name, sig, vals):
     """The entry point's status for the argument list `vals` (name -> tensor / None / int / float), no exception."""
     from tactilesr_amd._lib import load, ptr, stream, c_int, c_float
@@ -355,25 +343,6 @@ def test_contract_zero_input(T, kind):
 
 
 # ------------------------------------------------------------------------------------------- 6. refusals
-BAD_SCALES = [0.0, -1.0, NAN]
-
-
-def slice_mutations(cin, cout, with_res=True):
-    """Overrides that make a slice description invalid: not a multiple of 16, or leaving its buffer on either side."""
-    m = [{"cin": cin + 8}, {"cin": 0}, {"cin": -16}, {"in_ctot": cin + PAD - 8}, {"in_coff": 8}, {"out_ctot": cout + PAD - 8},
-         {"out_coff": 24}, {"in_coff": PAD + 16}, {"in_coff": -16}, {"out_coff": PAD + 16}, {"out_coff": -16},
-         {"in_ctot": cin - 16, "in_coff": 0}, {"out_ctot": cout - 16, "out_coff": 0}]
-    if with_res:
-        m += [{"res_ctot": cout + PAD - 8}, {"res_coff": 8}, {"res_coff": PAD + 16}, {"res_coff": -16},
-              {"res_ctot": cout - 16, "res_coff": 0}]
-    return m
-
-
-def common_mutations(required):
-    return ([{k: None} for k in required] + [{d: v} for d in ("B", "H", "W") for v in (0, -1)]
-            + [{"w_inv_scale": v} for v in BAD_SCALES])
-
-
 def check_refusals(name, sig, args, mutations, width, ref):
     """Every mutated argument list returns 1 and launches nothing; the unmodified one returns 0 and meets the bar."""
     preset = args["out_amax"].item()
@@ -390,29 +359,24 @@ def check_refusals(name, sig, args, mutations, width, ref):
 
 
 def test_f16s_refusals(T):
-    c = S.F16sCase(3, 16, 64, 1, 5, 3, True, True, True, 1, "zero", (16, 32, 48))
+    c = S.REFUSAL_CASES["f16s"]
     p = S.f16s_inputs(c)
     a = f16s_args(p, c.offs, prior=7.0)
-    muts = (common_mutations(["in", "w_packed", "out", "in_amax"]) + slice_mutations(16, 64)
-            + [{"cout": v} for v in (0, 32, 96, 256)] + [{"ks": v} for v in (-3, 0, 2, 4, 7)])
-    check_refusals("tsr_conv2d_fwd_f16s", F16S_SIG, a, muts, 64, S.f16s_ref(p))
+    check_refusals("tsr_conv2d_fwd_f16s", F16S_SIG, a, S.launch_mutations("f16s"), 64, S.f16s_ref(p))
 
 
 def test_pair_refusals(T):
-    c = S.PairCase(16, 1, 5, 3, True, True, 1, "zero", (16, 32))
+    c = S.REFUSAL_CASES["pair"]
     p = S.pair_inputs(c)
     a = pair_args(p, c.offs, prior=7.0)
-    muts = common_mutations(["in", "w_packed", "out", "in_amax"]) + slice_mutations(16, 128, with_res=False)
-    check_refusals("tsr_conv2d_fwd_f16s_pair", PAIR_SIG, a, muts, 128, S.pair_ref(p))
+    check_refusals("tsr_conv2d_fwd_f16s_pair", PAIR_SIG, a, S.launch_mutations("pair"), 128, S.pair_ref(p))
 
 
 def test_fuse1x1_refusals(T):
-    c = S.FuseCase(3, 16, 1, 5, 3, 1, True, True, True, True, 1, "zero", (16, 32, 48))
+    c = S.REFUSAL_CASES["fuse1x1"]
     p = S.fuse_inputs(c)
     a = fuse_args(p, c.offs, prior=7.0)
-    muts = (common_mutations(["in", "w_packed", "out", "in_amax", "w2_packed"]) + slice_mutations(16, 64)
-            + [{"w2_inv_scale": v} for v in BAD_SCALES] + [{"ks": v} for v in (-3, 0, 1, 2, 4, 7)])
-    check_refusals("tsr_conv2d_fwd_f16s_fuse1x1", FUSE_SIG, a, muts, 64, S.fuse_ref(p))
+    check_refusals("tsr_conv2d_fwd_f16s_fuse1x1", FUSE_SIG, a, S.launch_mutations("fuse1x1"), 64, S.fuse_ref(p))
 
 
 def test_pack_refusals(T):
@@ -421,30 +385,28 @@ def test_pack_refusals(T):
     SENT = 0x7A7A
     g = torch.Generator().manual_seed(9)
     n = 0
-    for cout, cin, ks in [(64, 16, 3), (128, 32, 5), (64, 128, 1)]:              # the last: fuse1x1's 1x1 half
+    for cout, cin, ks in S.PACK_SHAPES:
         w = dev(S.he(g, cout, cin, ks))
         wa = w.abs().max().reshape(1)
         buf = torch.full((load().tsr_conv_weight_bf16s_elems(cout, cin, ks, 2),), SENT, dtype=torch.int16, device="cuda")
-        shape = [{"cin": cin + 8}, {"cin": 0}, {"cin": -16}, {"cout": 0}, {"cout": 32}, {"cout": 96}, {"cout": 256},
-                 {"ks": -3}, {"ks": 0}, {"ks": 2}, {"ks": 4}, {"ks": 7}, {"w": None}, {"w_packed": None}]
         host = dict(w=w, w_packed=buf, cout=cout, cin=cin, ks=ks, wscale=S.host_wscale(w.cpu()))
-        for m in shape + [{"wscale": v} for v in BAD_SCALES]:
+        for m in S.pack_host_mutations(cin):
             assert raw("tsr_pack_conv_weight_f16s", PACK_SIG, dict(host, **m)) == 1, m
         devv = dict(w=w, w_packed=buf, cout=cout, cin=cin, ks=ks, w_amax=wa)
-        for m in shape + [{"w_amax": None}]:
+        for m in S.pack_dev_mutations(cin):
             assert raw("tsr_pack_conv_weight_f16s_dev", PACK_DEV_SIG, dict(devv, **m)) == 1, m
-        n += 2 * len(shape) + 4
+        n += len(S.pack_host_mutations(cin)) + len(S.pack_dev_mutations(cin))
         torch.cuda.synchronize()
         assert bool((buf == SENT).all()), "a refused pack wrote its buffer"
         assert raw("tsr_pack_conv_weight_f16s", PACK_SIG, host) == 0
         torch.cuda.synchronize()
         assert not bool((buf == SENT).all())
-    cin = 32
+    cin = S.PACK_PAIR_CIN
     w3, w5 = dev(S.he(g, 64, cin, 3)), dev(S.he(g, 64, cin, 5))
     wa = torch.maximum(w3.abs().max(), w5.abs().max()).reshape(1)
     buf = torch.full((load().tsr_conv_weight_pair_elems(cin),), SENT, dtype=torch.int16, device="cuda")
     pair = dict(w3=w3, w5=w5, w_packed=buf, cin=cin, wscale=S.host_wscale(w3.cpu(), w5.cpu()), w_amax=None)
-    muts = [{"w3": None}, {"w5": None}, {"w_packed": None}, {"cin": cin + 8}, {"cin": 0}, {"cin": -16}] + [{"wscale": v} for v in BAD_SCALES]
+    muts = S.pack_pair_mutations(cin)
     for m in muts:
         assert raw("tsr_pack_conv_weight_pair_f16s", PACK_PAIR_SIG, dict(pair, **m)) == 1, m
     torch.cuda.synchronize()

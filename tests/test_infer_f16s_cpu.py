@@ -1,6 +1,11 @@
 """CPU checks of tests/_infer_f16s.py: the fp64 references of tests/test_gpu_infer_fp16x3.py agree with torch compositions, the
 per-image checker finds a planted fault and names where it is, and every case table is well formed (slices inside their
-buffers, an image below one tile, a grid that is no multiple of 8, images of one magnitude)."""
+buffers, an image below one tile, a grid that is no multiple of 8, images of one magnitude).
+
+Refusals: every mutation in _infer_f16s of the three fp16x3 launches, of their pack routines and of the five dgrad pack
+routines comes back as status exactly 1.  The pointers are fake (never dereferenced); an argument list that is NOT refused
+reaches a launch, which without a device comes back as status 2.  tests/test_gpu_infer_fp16x3.py sends the launch and pack
+tables to real buffers."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -194,3 +199,68 @@ def test_images_of_a_case_have_one_magnitude(name):
             assert float(r.abs().max()) * 2 < prior
         if c.amax == "half":
             assert 0 < prior < float(r.abs().max())
+
+
+# ------------------------------------------------------------------------------------------------------- refusals
+def _refused(name, sig, base, muts):
+    for m in muts:
+        assert all(k in base for k in m), (name, m)
+        assert S.raw_fake(name, sig, dict(base, **m)) == 1, f"{name} accepted: {m}"
+    if not torch.cuda.is_available():           # without a device the valid list passes every check and fails at the launch
+        assert S.raw_fake(name, sig, base) == 2
+
+
+@pytest.mark.parametrize("kind", list(S.LAUNCHES))
+def test_every_mutation_is_refused(kind):
+    name, sig = S.LAUNCHES[kind]
+    muts = S.launch_mutations(kind)
+    assert len({repr(m) for m in muts}) == len(muts)
+    _refused(name, sig, S.fake_launch_args(kind), muts)
+
+
+def test_the_launch_tables_hold_every_refusal():
+    for kind in S.LAUNCHES:
+        muts = S.launch_mutations(kind)
+        want = [{"in": None}, {"w_packed": None}, {"out": None}, {"in_amax": None}, {"B": 0}, {"H": -1}, {"W": 0}, {"cin": 0},
+                {"cin": -16}, {"cin": 24}, {"in_coff": 8}, {"in_coff": -16}, {"out_coff": -16}, {"out_coff": 24}]
+        want += [{"w_inv_scale": v} for v in (0.0, -1.0)]
+        if kind != "pair":
+            want += [{"res_coff": -16}, {"res_coff": 8}, {"ks": 2}, {"ks": 7}]
+        if kind == "fuse1x1":
+            want += [{"w2_packed": None}, {"ks": 1}, {"w2_inv_scale": 0.0}]
+        if kind == "f16s":
+            want += [{"cout": 0}, {"cout": 96}]
+        assert all(w in muts for w in want), (kind, [w for w in want if w not in muts])
+        assert sum(1 for m in muts if any(isinstance(v, float) and v != v for v in m.values())) == (2 if kind == "fuse1x1" else 1)
+    assert {"ks": 1} not in S.launch_mutations("f16s")
+
+
+@pytest.mark.parametrize("cout,cin,ks", S.PACK_SHAPES)
+def test_pack_routines_refuse(cout, cin, ks):
+    ints = dict(w=S.FAKE, w_packed=S.FAKE, cout=cout, cin=cin, ks=ks)
+    _refused("tsr_pack_conv_weight_f16s", S.PACK_SIG, dict(ints, wscale=2.0 ** 14), S.pack_host_mutations(cin))
+    _refused("tsr_pack_conv_weight_f16s_dev", S.PACK_DEV_SIG, dict(ints, w_amax=S.FAKE), S.pack_dev_mutations(cin))
+
+
+def test_pair_pack_refuses():
+    cin = S.PACK_PAIR_CIN
+    base = dict(w3=S.FAKE, w5=S.FAKE, w_packed=S.FAKE, cin=cin, wscale=2.0 ** 14, w_amax=None)
+    _refused("tsr_pack_conv_weight_pair_f16s", S.PACK_PAIR_SIG, base, S.pack_pair_mutations(cin))
+    if not torch.cuda.is_available():
+        assert S.raw_fake("tsr_pack_conv_weight_pair_f16s", S.PACK_PAIR_SIG, dict(base, wscale=0.0, w_amax=S.FAKE)) == 2   # w_amax replaces wscale
+
+
+@pytest.mark.parametrize("name", list(S.DGRAD_PACK_SIGS))
+def test_dgrad_pack_routines_refuse(name):
+    """NULL pointers, cout not a multiple of 16, nprime not 64 / 128, ci0 < 0, ci0 + nprime > cin, a bad ks."""
+    sig = S.DGRAD_PACK_SIGS[name]
+    base = dict(S.DGRAD_PACK_VALID, w=S.FAKE, w_packed=S.FAKE, w_amax=S.FAKE)
+    _refused(name, sig, base, S.dgrad_pack_mutations(name))
+    if not torch.cuda.is_available():
+        assert S.raw_fake(name, sig, dict(base, nprime=64, ci0=128)) == 2            # the other width, ending the buffer
+    if "wscale:f" in sig:
+        for v in S.BAD_SCALES:
+            assert S.raw_fake(name, sig, dict(base, wscale=v)) == 1, v
+    if "nsplit:i" in sig:
+        for v in (0, 4, -1):
+            assert S.raw_fake(name, sig, dict(base, nsplit=v)) == 1, v
