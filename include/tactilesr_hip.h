@@ -199,8 +199,8 @@ int tsr_pack_w2_b16k(const float* w2_64x128, void* w_packed, void* stream);
  * (arguments as tsr_pack_conv_weight_dgrad_bf16s, nprime = 128 or 64; tsr_conv_weight_b16k_elems(nprime, cout, ks) elements).
  * Slab entries as for nsplit = -1 (tsr_conv2d_slab_entries_ex accepts -3 / -4).  The predicate also accepts (128, 64, 1): the
  * masked dgrad of a 1x1 conv with 64 output channels (epi_mode 2, no partial gradient) as a streaming kernel without LDS
- * (csrc/conv1x1_b16k.hip; one slab entry per workgroup: ask tsr_conv2d_slab_entries_ex with nsplit = -3).  The same nsplit = -3 runs the FORWARD launches of that shape class (C_out = 128, C_in a
- * multiple of 32, 3x3 / 5x5, plain input) there too: epi_mode 1 (raw output + Welford partials; weights from
+ * (csrc/conv1x1_b16k.hip; one slab entry per workgroup: ask tsr_conv2d_slab_entries_ex with nsplit = -3).  The same nsplit = -3 runs the FORWARD launches of that shape class (C_out = 64 or 128,
+ * C_in a multiple of 32, 3x3 / 5x5, plain input: the predicate called as (cout, cin, ks)) there too: epi_mode 1 (raw output + Welford partials; weights from
  * tsr_pack_conv_weight_b16k) and epi_mode 0 with that pack; nsplit = -4 is epi_mode 1 of the stage-1 pair of an MSRB
  * (conv_3_1 || conv_5_1 as one 5x5 launch with 128 output channels, weights from tsr_pack_conv_weight_b16k_pair). */
 int tsr_conv2d_ex_dgrad_b16k(int nprime, int cout, int ks);
@@ -298,6 +298,22 @@ typedef struct tsr_conv_desc {
                              w_inv_scale (no host round trip for the weight scale) */
 } tsr_conv_desc;
 
+/* Refusals of tsr_conv2d_ex (status 1, nothing is launched; out, slab, slab_cnt and out_amax are untouched; checked launch by
+ * launch in tests/test_gpu_conv_ex_b16k.py, without a device in tests/test_conv_ex_cases_cpu.py -- the table is
+ * tests/_conv_ex_cases.py).  Every nsplit: desc = NULL; a NULL in, w_packed or out; B, H, W or cin <= 0; cin, any ctot or any
+ * coff not a multiple of 16; a negative coff or a slice that leaves its buffer (coff + channels > ctot) for in, out, res (when
+ * given) and mask (epi_mode 2); cout not in {64, 128}; ks not in {1, 3, 5}; epi_mode outside 0..2; epi_mode 1 without slab or
+ * without slab_cnt; epi_mode 2 without mask; bn_a without bn_b or without slab (epi_mode 2; bn_a is read in no other mode); in_scale
+ * without in_shift or the reverse, res_scale without res_shift or the reverse; nsplit outside -4..3.
+ *   -2: a NULL in_amax; w_amax NULL and w_inv_scale not > 0 (0, negative, NaN).
+ *   -1: the streaming 1x1 form (ks 1, C_out 64, epi_mode 0) keeps the whole weight in LDS: cin * 136 bytes > 72 KB (cin >= 544).
+ *   -3, ks in {3, 5}: C_in not a multiple of 32 (48, 16); a virtual input (in_scale) or a virtual residual (res_scale);
+ *       8 * in_ctot * H * W >= 2^31 (32-bit halo offsets inside a 4-image group); epi_mode 1 / 2 as above.
+ *   -3, ks = 1: only two forms exist.  epi_mode 0 = the forward on a VIRTUAL input: refused with a plain input, with scale, with
+ *       C_out != 64 or C_in not in {128, 256}, or 2 * in_ctot * H * W >= 2^31.  epi_mode 2 = the masked dgrad with N = cout = 128 and
+ *       K = cin = 64: refused with res, scale, shift or an input transform, with N = 64 or K = 128, beyond the offset bound above.  epi_mode 1: always.
+ *   -4: anything but ks 5, cout 128, epi_mode 1 with slab and slab_cnt, a plain input and C_in a multiple of 32 (ks 3, cout 64,
+ *       epi_mode 0 or 2, no slab, a virtual input, C_in 48); the -3 offset bound. */
 int tsr_conv2d_ex(const tsr_conv_desc* desc, void* stream);
 int tsr_conv2d_slab_entries(int B, int H, int W);
 /* Entries the launch described by (cout, ks, nsplit) writes -- the count to hand to tsr_bn_stats_finalize /

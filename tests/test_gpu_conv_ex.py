@@ -17,6 +17,13 @@ Arithmetics (nsplit), kernels, images per workgroup (= statistics-slab entries p
     bf16   -1   conv_mfma_split16.hip IO16 (3x3 / 5x5)                               4
                 IO16 1x1 tiled (C_out 128, or any launch with slabs)                 2
                 conv1x1_b16_ex_kernel (1x1, C_out 64, epi_mode 0: streaming)         4 (no slabs)
+    b16k   -3   conv_b16k.hip TRAIN / DGRAD / PLAIN (3x3 / 5x5, C_in % 32 == 0)      4     tests/test_gpu_conv_ex_b16k.py: these
+           -4   conv_b16k.hip PAIR_TRAIN (the stage-1 pair, 5x5 -> 64 | 64)          4     tables, more rows and the refusal
+           -3   conv1x1_b16k.hip (1x1: virtual-input forward 128 / 256 -> 64,        1 entry per workgroup (masked dgrad)
+                masked dgrad 64 -> 128)                                                    matrix of tsr_conv2d_ex
+
+The tables, the pure helpers and the fp64 references live in tests/_conv_ex_cases.py (checked without a device by
+tests/test_conv_ex_cases_cpu.py).
 
 Case lists -- hand-picked against the tiling (8x8 pixel tiles; 2 or 4 images per workgroup; channel blocks of 16 paired into
 K = 32 steps), every row runs with EVERY arithmetic.  `K` is the launch's reduction width (C_in of a forward, the conv's
@@ -72,13 +79,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-pytestmark = pytest.mark.gpu
+from _conv_ex_cases import (NAN, IMPLS, TOL, SUM_TOL, GUARD, FWD1_CASES, FWD0_CASES, DGRAD_CASES,         # noqa: F401
+                            q16, fma32, relerr, images_per_workgroup, operands, check_tensor, entry_counts, check_welford_host)
 
-NAN = float("nan")
-IMPLS = {"f32": 0, "bf16x6": 3, "fp16x3": -2, "bf16op": 1, "bf16x3": 2, "bf16": -1}
-TOL = {0: 1e-5, 3: 1e-5, -2: 1e-5, 1: 1e-5, 2: 1e-4, -1: 1e-5}          # outputs (fp32 tensors) and Welford statistics
-SUM_TOL = {0: 1e-5, 3: 1e-5, -2: 1e-5, 1: 1e-5, 2: 1e-4, -1: 1e-4}      # BatchNorm-backward sums
-GUARD = 8                                                               # NaN entries behind the slab's last entry
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -90,15 +94,6 @@ def T():
 
 
 # ---------------------------------------------------------------------------------------------------------------- plumbing
-def q16(t):
-    return t.bfloat16().float()
-
-
-def fma32(x, s, t):
-    """fp32 fma(x, s_c, t_c) per channel, as the kernels form a virtual input: the product is exact in fp64."""
-    return (x.double() * s.double().view(1, -1, 1, 1) + t.double().view(1, -1, 1, 1)).float()
-
-
 def cb16(x, ctot, coff, dtype=torch.float32):
     """NCHW (cpu) -> flat CB16 device buffer [B][ctot/16][H*W][16]; channels outside [coff, coff + C) are NaN."""
     B, C, H, W = x.shape
@@ -111,16 +106,6 @@ def nchw(buf, B, ctot, H, W):
     return buf.cpu().float().view(B, ctot // 16, H * W, 16).permute(0, 1, 3, 2).reshape(B, ctot, H, W)
 
 
-def relerr(got, ref):
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max().clamp_min(1e-30))
-
-
-def images_per_workgroup(ns, ks):
-    """include/tactilesr_hip.h, tsr_conv2d_slab_entries_ex: 4 for the 3x3 / 5x5 launches of fp16x3 and of the one-plane bf16
-    forms (bf16op, bf16 storage), 2 for everything else."""
-    return 4 if ks > 1 and ns in (-2, 1, -1) else 2
-
-
 def act_dtype(ns):
     return torch.bfloat16 if ns == -1 else torch.float32
 
@@ -129,38 +114,11 @@ def dev(t):
     return None if t is None else t.cuda().contiguous()
 
 
-def operands(ns, z, w, s=None, t=None):
-    """(stored input, fp64 activation the MFMA sees, fp64 weight the MFMA sees) for arithmetic `ns`."""
-    zs = q16(z) if ns == -1 else z
-    a = F.relu(fma32(zs, s, t)) if s is not None else zs
-    if ns in (1, -1):
-        return zs, q16(a).double(), q16(w).double()
-    return zs, a.double(), w.double()
-
-
 def pack_fwd(ns, w):
     from tactilesr_amd.model._train import _pack
     wd = dev(w)
     wa = wd.abs().max().reshape(1) if ns == -2 else None
     return _pack(wd, w.shape[0], w.shape[1], w.shape[2], ns, wa), wa
-
-
-def check_tensor(ns, got, ref):
-    """The bar of arithmetic `ns` on one output tensor (got fp32 values, ref fp64); returns the figures as text."""
-    assert torch.isfinite(got).all()
-    if ns == -1:
-        r16 = q16(ref.float())
-        d = (got - r16).abs()
-        same = float((d == 0).float().mean())
-        bad = d > torch.maximum(1.01 * r16.abs() * 2.0 ** -7, torch.full_like(r16, 3e-6 * float(r16.abs().max())))
-        txt = f"identical {same:.5f}, beyond one ulp {int(bad.sum())}"
-        assert not bad.any(), txt
-        if got.numel() >= 100:
-            assert same >= 0.99, txt
-        return txt
-    e = relerr(got, ref)
-    assert e < TOL[ns], e
-    return f"{e:.1e}"
 
 
 def check_outside_untouched(full, coff, c):
@@ -171,46 +129,16 @@ def slab_geometry(ns, ks, B, H, W, cout):
     """(entries the library reports, images per workgroup, expected valid-pixel count of every entry)."""
     from tactilesr_amd._lib import load
     img = images_per_workgroup(ns, ks)
-    ty, tx = (H + 7) // 8, (W + 7) // 8
-    groups = (B + img - 1) // img
-    entries = load().tsr_conv2d_slab_entries_ex(B, H, W, cout, ks, ns)
-    assert entries == groups * ty * tx * img
-    rows = torch.tensor([min(8, H - 8 * i) for i in range(ty)], dtype=torch.float64)
-    cols = torch.tensor([min(8, W - 8 * i) for i in range(tx)], dtype=torch.float64)
-    px = (rows[:, None] * cols[None, :]).reshape(1, -1, 1)
-    present = (torch.arange(groups * img) < B).double().view(groups, 1, img)
-    return entries, img, (px * present).reshape(-1)
+    entries, want_cnt = entry_counts(img, B, H, W)
+    assert entries == load().tsr_conv2d_slab_entries_ex(B, H, W, cout, ks, ns)
+    return entries, img, want_cnt
 
 
 def check_welford(ns, slab, cnt, ref, ks, tol, check_var=True):
     """epi_mode 1 slabs against the fp64 output `ref`: guard band, counts, per-entry means, Chan-merged mean / variance."""
     B, cout, H, W = ref.shape
-    entries, img, want_cnt = slab_geometry(ns, ks, B, H, W, cout)
-    sl = slab.cpu().double().view(entries + GUARD, cout, 2)
-    n_e = cnt.cpu().double()
-    assert torch.isnan(sl[entries:]).all() and torch.isnan(n_e[entries:]).all(), "an entry was written out of range"
-    assert torch.isfinite(sl[:entries]).all() and torch.isfinite(n_e[:entries]).all(), "an entry was not written"
-    sl, n_e = sl[:entries], n_e[:entries]
-    assert torch.equal(n_e, want_cnt), "per-entry valid-pixel counts"
-    assert float(n_e.sum()) == B * H * W
-    # every entry's own mean: entry (group, tile, slot) = image group * img + slot, tile (ty, tx)
-    tx_n, tiles = (W + 7) // 8, ((H + 7) // 8) * ((W + 7) // 8)
-    scale = float(ref.abs().max())
-    e_ent = 0.0
-    for e in range(entries):
-        b, t = (e // (tiles * img)) * img + e % img, (e // img) % tiles
-        if b >= B:
-            assert float(sl[e].abs().max()) == 0.0          # an absent image: count 0, mean 0, M2 0
-            continue
-        y0, x0 = (t // tx_n) * 8, (t % tx_n) * 8
-        e_ent = max(e_ent, float((sl[e, :, 0] - ref[b, :, y0:y0 + 8, x0:x0 + 8].mean(dim=(1, 2))).abs().max()) / scale)
-    N = float(n_e.sum())
-    mean = (sl[:, :, 0] * n_e[:, None]).sum(0) / N
-    m2 = (sl[:, :, 1] + n_e[:, None] * (sl[:, :, 0] - mean[None]) ** 2).sum(0)
-    rm, rv = ref.mean(dim=(0, 2, 3)), ref.var(dim=(0, 2, 3), unbiased=False)
-    e_m, e_v = float((mean - rm).abs().max()) / scale, float((m2 / N - rv).abs().max() / rv.max())
-    assert e_ent < tol and e_m < tol and (e_v < tol or not check_var), (e_ent, e_m, e_v)
-    return f"entry means {e_ent:.1e}, mean {e_m:.1e}, var {e_v:.1e}"
+    _, img, _ = slab_geometry(ns, ks, B, H, W, cout)
+    return check_welford_host(slab.cpu(), cnt.cpu(), ref, img, tol, check_var)
 
 
 def test_every_train_arithmetic_is_parametrized():
@@ -219,21 +147,6 @@ def test_every_train_arithmetic_is_parametrized():
 
 
 # ------------------------------------------------------------------------------------------- 1. forward, epi_mode 1
-# (ks, cin, cout, B, H, W, virtual input, in_coff, out_coff, out_amax prior: None = no out_amax)
-FWD1_CASES = [
-    (3, 64, 64, 3, 40, 40, True, 16, 32, 0.0),
-    (5, 128, 128, 2, 13, 21, True, 32, 16, 1.0e6),
-    (1, 256, 64, 5, 9, 17, True, 16, 16, None),
-    (3, 16, 128, 1, 5, 3, False, 32, 32, 0.0),
-    (5, 48, 64, 2, 1, 1, True, 16, 32, None),
-    (1, 128, 128, 3, 13, 21, False, 32, 16, 0.0),
-    (3, 128, 64, 70, 12, 12, False, 16, 32, None),
-    (5, 64, 128, 3, 40, 40, False, 16, 16, 0.0),
-    (3, 256, 128, 2, 9, 17, True, 32, 16, None),
-    (1, 64, 64, 1, 40, 40, True, 16, 32, 0.0),
-]
-
-
 def _cid(c):
     return "-".join("x" if v is None else str(v) for v in c)
 
@@ -284,20 +197,6 @@ def test_forward_raw_output_and_welford_slabs(T, case, impl):
 
 
 # ------------------------------------------------------------------------------------------- 2. forward, epi_mode 0
-# (ks, cin, cout, B, H, W, virtual input, residual: None / "plain" / "virtual", relu, scale, in_coff, out_coff, res_coff)
-FWD0_CASES = [
-    (1, 256, 64, 2, 40, 40, True, "plain", 1, False, 16, 32, 16),
-    (1, 256, 64, 3, 13, 21, True, "virtual", 1, False, 32, 16, 32),
-    (3, 64, 64, 5, 9, 17, False, "plain", 1, False, 16, 32, 0),
-    (3, 64, 64, 1, 5, 3, False, None, 1, False, 32, 16, 0),
-    (1, 128, 128, 2, 1, 1, True, None, 0, False, 16, 32, 0),
-    (5, 48, 128, 3, 13, 21, True, "virtual", 0, True, 32, 16, 32),
-    (5, 16, 64, 2, 9, 17, False, "plain", 0, False, 16, 16, 32),
-    (1, 64, 64, 70, 12, 12, False, "plain", 1, False, 32, 32, 16),
-    (3, 128, 128, 2, 40, 40, True, "plain", 1, False, 16, 32, 32),
-]
-
-
 @pytest.mark.parametrize("impl", list(IMPLS))
 @pytest.mark.parametrize("case", FWD0_CASES, ids=_cid)
 def test_forward_affine_residual_relu_epilogue(T, case, impl):
@@ -351,23 +250,6 @@ def test_forward_affine_residual_relu_epilogue(T, case, impl):
 
 
 # ------------------------------------------------------------------------------------------- 3. data gradient
-# (ks, K = the conv's C_out, cin of the conv, N = nprime, ci0, B, H, W, residual, form, scale,
-#  dz_coff, out_coff, res_coff, mask_coff);  form: "bn" = epi_mode 2 + sums, "mask" = epi_mode 2 without bn_a,
-#  "partial" = epi_mode 0 without a mask
-DGRAD_CASES = [
-    (3, 64, 64, 64, 0, 3, 40, 40, True, "bn", False, 16, 32, 16, 32),
-    (5, 128, 192, 128, 64, 2, 13, 21, True, "bn", True, 32, 16, 32, 16),
-    (1, 64, 256, 128, 128, 5, 9, 17, False, "bn", False, 16, 16, 0, 32),
-    (3, 16, 64, 64, 0, 1, 5, 3, True, "bn", False, 32, 32, 16, 16),
-    (5, 48, 128, 64, 64, 2, 1, 1, True, "mask", False, 16, 32, 32, 16),
-    (1, 256, 64, 64, 0, 3, 13, 21, False, "partial", True, 32, 16, 0, 0),
-    (3, 128, 128, 128, 0, 70, 12, 12, True, "bn", False, 16, 32, 32, 16),
-    (5, 64, 64, 64, 0, 3, 40, 40, True, "partial", False, 16, 16, 32, 0),
-    (3, 256, 128, 128, 0, 2, 9, 17, True, "bn", False, 32, 16, 0, 48),
-    (1, 128, 128, 64, 64, 1, 40, 40, True, "bn", False, 16, 32, 16, 32),
-]
-
-
 @pytest.mark.parametrize("impl", list(IMPLS))
 @pytest.mark.parametrize("case", DGRAD_CASES, ids=_cid)
 def test_dgrad_mask_and_bn_sums_direct(T, case, impl):

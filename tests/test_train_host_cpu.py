@@ -401,8 +401,9 @@ def test_seqs_index_table_follows_the_reference_arithmetic():
 
 def test_conv_slab_entry_counts_follow_the_images_per_workgroup_of_each_form():
     """include/tactilesr_hip.h: tsr_conv2d_slab_entries_ex = ceil(B / img) * tiles * img with img = 4 for the 3x3 / 5x5
-    launches of fp16x3 (-2) and of the one-plane bf16 forms (1, -1), 2 for every other form; tsr_conv2d_slab_entries is
-    the 2-image count.  Host arithmetic only: no device is touched."""
+    launches of fp16x3 (-2) and of the one-plane bf16 forms (1, -1, and conv_b16k's -3 / -4), 2 for every other form;
+    tsr_conv2d_slab_entries is the 2-image count; -3 with ks = 1 is one entry per streaming workgroup.  Host arithmetic only:
+    no device is touched."""
     from tactilesr_amd import _lib
     lib = _lib.load()
     for B in (1, 2, 3, 4, 5, 70):
@@ -417,6 +418,19 @@ def test_conv_slab_entry_counts_follow_the_images_per_workgroup_of_each_form():
                         assert got == ((B + img - 1) // img) * tiles * img, (B, H, W, cout, ks, ns, got)
                         if img == 2:
                             assert got == lib.tsr_conv2d_slab_entries(B, H, W)
+            # conv_b16k / conv1x1_b16k (bf16 storage, -3; the stage-1 pair, -4): 4 images per workgroup for 3x3 / 5x5; the
+            # streaming 1x1 kernel of -3 writes ONE entry per workgroup, min(B * ceil(H * W / 16), 2048); 1x1 under -4 (no
+            # such launch) counts like every other form
+            for ns in (-3, -4):
+                for cout in (64, 128):
+                    for ks in (3, 5):
+                        got = lib.tsr_conv2d_slab_entries_ex(B, H, W, cout, ks, ns)
+                        assert got == ((B + 3) // 4) * tiles * 4 == lib.tsr_conv2d_slab_entries_ex(B, H, W, cout, ks, -1), (B, H, W, cout, ks, ns)
+                    got = lib.tsr_conv2d_slab_entries_ex(B, H, W, cout, 1, ns)
+                    want = min(B * ((H * W + 15) // 16), 2048) if ns == -3 else lib.tsr_conv2d_slab_entries(B, H, W)
+                    assert got == want, (B, H, W, cout, ns, got)
+    for B, H, W, want in ((2048, 40, 40, 2048), (129, 4, 4, 129), (128, 5, 7, 384), (683, 5, 7, 2048), (682, 5, 7, 2046)):
+        assert lib.tsr_conv2d_slab_entries_ex(B, H, W, 128, 1, -3) == want      # the cap, and just below it
 
 
 def _engine_wgrad_shapes():
