@@ -395,6 +395,27 @@ int tsr_bn_bwd_apply(float* g, int g_ctot, int g_coff, const float* z, int z_cto
                      const float* c1, const float* c2, const float* c3, int C, int B, int HW,
                      float* out_amax /* optional: max|g| after the update */, void* stream);
 
+/* nn.BatchNorm2d in EVAL mode inside a training module (`model.train()` then `bn.eval()` on some layers of
+ * model/tactileSR_model.py:38,42,48,169-187: torch then normalises those layers with running_mean / running_var and leaves
+ * the statistics alone).  tsr_bn_eval_vectors: the four forward vectors of tsr_bn_stats_finalize from the running
+ * statistics, in double: invstd = 1/sqrt(running_var + eps), scale = gamma*invstd, shift = beta + (bias - running_mean)*scale,
+ * xhat_a = invstd, xhat_b = (bias - running_mean)*invstd (to apply on the bias-free conv output; bias may be NULL).  One
+ * launch, nothing is updated; C > 0 and a multiple of 16.
+ * tsr_bn_bwd_finalize_eval: tsr_bn_bwd_finalize's slab reduction, emitting only dgamma = sum g*xhat and dbeta = sum g
+ * (C = 64 or 128; work: 512*C*3 doubles).
+ * tsr_bn_bwd_apply_eval: dz = scale * g, i.e. g[:, g_coff : g_coff + C] *= scale[c] in place on a CB16 tensor -- one read and
+ * one write per element, no z (tsr_bn_bwd_apply moves three tensors).  C, g_ctot, g_coff multiples of 16, 0 <= g_coff,
+ * g_coff + C <= g_ctot, B > 0, HW > 0; status 1 before any launch otherwise.  out_amax as for tsr_bn_bwd_apply. */
+int tsr_bn_eval_vectors(const float* bias, const float* gamma, const float* beta, const float* running_mean,
+                        const float* running_var, float eps, int C, float* scale, float* shift, float* xhat_a,
+                        float* xhat_b, void* stream);
+int tsr_bn_bwd_finalize_eval(const float* slab, int entries, int C, float* dgamma, float* dbeta, double* work,
+                             void* stream);
+int tsr_bn_bwd_apply_eval(float* g, int g_ctot, int g_coff, const float* scale, int C, int B, int HW,
+                          float* out_amax /* optional: max|g| after the update */, void* stream);
+/* (the bf16 CB16 form: fp32 product, one rounding on the store) */
+int tsr_bn_bwd_apply_eval_b16(void* g, int g_ctot, int g_coff, const float* scale, int C, int B, int HW, void* stream);
+
 /* Backward of tsr_stem_fwd's conv weight: slab[s][64][3][3][3] partials, s < nsplit, any nsplit >= 1 (the taxel gradient is
  * tsr_stem_dgrad).  Tall images are cut into row bands so that one band (+ halo) of the upsampled image fits in LDS: the
  * bands are spread over the splits as far as they divide nsplit, a workgroup walks the rest; status 1 only when three

@@ -67,6 +67,10 @@ SIGNATURES = {
     "tsr_cb16_stats": [_P, _I, _I, _I, _I, _P, _P, _P],
     "tsr_bn_bwd_finalize": [_P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "tsr_bn_bwd_apply": [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
+    "tsr_bn_eval_vectors": [_P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P],
+    "tsr_bn_bwd_finalize_eval": [_P, _I, _I, _P, _P, _P, _P],
+    "tsr_bn_bwd_apply_eval": [_P, _I, _I, _P, _I, _I, _I, _P, _P],
+    "tsr_bn_bwd_apply_eval_b16": [_P, _I, _I, _P, _I, _I, _I, _P],
     "tsr_stem_wgrad": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
     "tsr_stem_dgrad": [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P],
     "tsr_head_bwd": [_P, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P],

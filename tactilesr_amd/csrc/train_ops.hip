@@ -224,6 +224,134 @@ extern "C" int tsr_bn_bwd_apply_b16(void* g, int g_ctot, int g_coff, const void*
 }
 
 // ------------------------------------------------------------------------------------------
+// A BatchNorm2d layer in EVAL mode inside a training module (nn.BatchNorm2d.eval() under model.train(): it normalises with
+// its running statistics and leaves them alone).  Forward: the same four per-channel vectors tsr_bn_stats_finalize hands
+// out, from the running statistics; nothing is updated.  z is the bias-free accumulator, so the conv bias enters here.
+// Backward: dz = scale * g (no batch-statistics terms), dgamma = sum g*xhat, dbeta = sum g.
+// ------------------------------------------------------------------------------------------
+__global__ void bn_eval_vectors_kernel(const float* __restrict__ bias, const float* __restrict__ gamma,
+                                       const float* __restrict__ beta, const float* __restrict__ running_mean,
+                                       const float* __restrict__ running_var, float eps, int C,
+                                       float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ xa,
+                                       float* __restrict__ xb) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const double invstd = 1.0 / sqrt((double)running_var[c] + (double)eps);
+  const double d = (bias ? (double)bias[c] : 0.0) - (double)running_mean[c];
+  const double sc = (double)gamma[c] * invstd;
+  scale[c] = (float)sc;
+  shift[c] = (float)((double)beta[c] + d * sc);
+  xa[c] = (float)invstd;
+  xb[c] = (float)(d * invstd);
+}
+
+extern "C" int tsr_bn_eval_vectors(const float* bias, const float* gamma, const float* beta, const float* running_mean,
+                                   const float* running_var, float eps, int C, float* scale, float* shift,
+                                   float* xhat_a, float* xhat_b, void* stream) {
+  if (!gamma || !beta || !running_mean || !running_var || !scale || !shift || !xhat_a || !xhat_b || C <= 0 || (C & 15))
+    return TSR_ERR_ARG;
+  hipLaunchKernelGGL(bn_eval_vectors_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, bias, gamma, beta,
+                     running_mean, running_var, eps, C, scale, shift, xhat_a, xhat_b);
+  return tsr_check_launch();
+}
+
+// the tail of bn_bwd_final_kernel without the coefficients: part[k][c] = {entries, sum g, sum g*xhat}
+__global__ void bn_bwd_final_eval_kernel(const double* __restrict__ part, int nblocks, int C, float* __restrict__ dgamma,
+                                         float* __restrict__ dbeta) {
+  __shared__ double sh[256 * 2];
+  const int tid = threadIdx.x, cl = tid & 15, kl = tid >> 4;
+  const int c = blockIdx.x * 16 + cl;
+  double s1 = 0, s2 = 0;
+  for (int k = kl; k < nblocks; k += 16) {
+    const double* p = part + ((size_t)k * C + c) * 3;
+    s1 += p[1]; s2 += p[2];
+  }
+  sh[tid * 2 + 0] = s1; sh[tid * 2 + 1] = s2;
+  __syncthreads();
+  if (kl != 0) return;
+  for (int k = 1; k < 16; ++k) { s1 += sh[(k * 16 + cl) * 2 + 0]; s2 += sh[(k * 16 + cl) * 2 + 1]; }
+  dbeta[c] = (float)s1;
+  dgamma[c] = (float)s2;
+}
+
+extern "C" int tsr_bn_bwd_finalize_eval(const float* slab, int entries, int C, float* dgamma, float* dbeta, double* work,
+                                        void* stream) {
+  if (!slab || !dgamma || !dbeta || !work || entries <= 0 || (C != 64 && C != 128)) return TSR_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3(RED_BLOCKS), dim3(256), 0, st, slab, (const float*)nullptr, entries,
+                     C, 1, work);
+  hipLaunchKernelGGL(bn_bwd_final_eval_kernel, dim3(C / 16), dim3(256), 0, st, work, RED_BLOCKS, C, dgamma, dbeta);
+  return tsr_check_launch();
+}
+
+// g[:, gcoff:gcoff+C] *= scale   (CB16, in place): one read and one write per element, no z.  The layout of
+// bn_bwd_apply_kernel: one workgroup per (image, 16-channel block), a thread keeps one channel quad of `scale` and has UNR
+// independent 16-B loads in flight.
+template <bool B16>
+__global__ __launch_bounds__(256) void bn_bwd_apply_eval_kernel(float* __restrict__ g, int g_ctot, int g_coff,
+                                                                const float* __restrict__ scale, int C, int HW,
+                                                                float* __restrict__ out_amax) {
+  constexpr int UNR = 5;
+  const int nblk = C >> 4;
+  const int b = blockIdx.x / nblk, blk = blockIdx.x - b * nblk;
+  const int c = blk * 16 + (threadIdx.x & 3) * 4;
+  const size_t gbase = (((size_t)b * (g_ctot >> 4) + ((g_coff >> 4) + blk)) * HW) * 16;
+  const f32x4 k1 = *(const f32x4*)(scale + c);
+  const int n4 = HW * 4;
+  float amax = 0.f;
+  for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * UNR) {
+    f32x4 gv[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int i = i0 + u * 256;
+      gv[u] = tsr_ld4<B16>(g, gbase + (size_t)(i < n4 ? i : i0) * 4);       // (tail: re-read the first item, not stored)
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int i = i0 + u * 256;
+      if (i < n4) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          gv[u][j] *= k1[j];
+          amax = fmaxf(amax, fabsf(gv[u][j]));
+        }
+        tsr_st4<B16>(g, gbase + (size_t)i * 4, gv[u]);
+      }
+    }
+  }
+  if (out_amax) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    if ((threadIdx.x & 63) == 0) publish_amax(out_amax, amax);
+  }
+}
+
+static int bn_apply_eval_args(const void* g, int g_ctot, int g_coff, const float* scale, int C, int B, int HW) {
+  if (!g || !scale || C <= 0 || (C & 15) || g_ctot <= 0 || (g_ctot & 15) || g_coff < 0 || (g_coff & 15) ||
+      (long long)g_coff + C > g_ctot)
+    return TSR_ERR_ARG;
+  if (B <= 0 || HW <= 0 || HW > 0x7fffffff / 4 || (long long)B * (C >> 4) > 0x7fffffffLL) return TSR_ERR_ARG;
+  return TSR_OK;
+}
+
+extern "C" int tsr_bn_bwd_apply_eval(float* g, int g_ctot, int g_coff, const float* scale, int C, int B, int HW,
+                                     float* out_amax, void* stream) {
+  if (bn_apply_eval_args(g, g_ctot, g_coff, scale, C, B, HW)) return TSR_ERR_ARG;
+  hipLaunchKernelGGL(bn_bwd_apply_eval_kernel<false>, dim3(B * (C >> 4)), dim3(256), 0, (hipStream_t)stream, g, g_ctot,
+                     g_coff, scale, C, HW, out_amax);
+  return tsr_check_launch();
+}
+
+// the same on a bf16 CB16 tensor: fp32 product, rounded once on the store
+extern "C" int tsr_bn_bwd_apply_eval_b16(void* g, int g_ctot, int g_coff, const float* scale, int C, int B, int HW,
+                                         void* stream) {
+  if (bn_apply_eval_args(g, g_ctot, g_coff, scale, C, B, HW)) return TSR_ERR_ARG;
+  hipLaunchKernelGGL(bn_bwd_apply_eval_kernel<true>, dim3(B * (C >> 4)), dim3(256), 0, (hipStream_t)stream, (float*)g,
+                     g_ctot, g_coff, scale, C, HW, (float*)nullptr);
+  return tsr_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------
 // stem backward: dW[64][3][3][3] of Upsample+Conv2d(3->64) (the taxel gradient: stem_dgrad_kernel below)
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void bilin_src_t(int dst, float scale, int n_in, int& i0, int& i1, float& lam) {

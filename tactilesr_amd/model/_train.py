@@ -43,6 +43,9 @@ def check_trainable_size(H, W):
 # incoming dout) and has no producer.  The BatchNorm sums a dgrad(bn=True) epilogue leaves in the statistics slab are an
 # output of that dgrad (label "<tensor>.sums"), consumed by the bn_bwd_finalize behind it; the coefficients a finalize
 # writes ("<bn>.coef") are consumed by its bn_bwd_apply, which turns the masked gradient g into dz in place.
+# A BatchNorm layer in eval mode inside the training module (`bn_eval`: its path; running statistics, dz = scale * g) has
+# a bn_bwd_apply that needs no coefficients and a bn_bwd_finalize that only serves dgamma / dbeta: when neither is wanted
+# the finalize goes and the dgrad in front of it leaves no sums.
 # ---------------------------------------------------------------------------------------------------------------------
 class Record(NamedTuple):
     kind: str           # head_bwd | head_dgrad | wgrad | dgrad | bn_bwd_finalize | bn_bwd_apply | stem_wgrad | stem_dgrad
@@ -67,26 +70,46 @@ def _res_records(p, dpre):
     ]
 
 
-def _msrb_records(p, dpre, virtual):
+def bn_members(layer):
+    """Module paths of the BatchNorm layers behind a record's `layer`: itself, or for layers that share a launch
+    ("<block>.conv_3_1.1|conv_5_1.1", the stage-1 pair of an MSRB) each of them."""
+    head, _, tail = layer.partition("|")
+    return (head, head[:len(head) - len(tail)] + tail) if tail else (head,)
+
+
+def bn_held(layer, bn_eval):
+    """Whether the BatchNorm record `layer` runs the eval-mode backward: every layer behind it is in `bn_eval` (a mixed
+    stage-1 pair keeps the batch-statistics launches; the engine zeroes the statistics terms of its held half)."""
+    return all(n in bn_eval for n in bn_members(layer))
+
+
+def _bn_records(bn, g, dz, params, bn_eval):
+    """The two BatchNorm-backward records behind the dgrad that left the masked gradient `g` and its sums."""
+    if bn_held(bn, bn_eval):
+        return [Record("bn_bwd_finalize", bn, (g + ".sums",), (), params), Record("bn_bwd_apply", bn, (g,), (dz,), ())]
+    return [Record("bn_bwd_finalize", bn, (g + ".sums",), (bn + ".coef",), params),
+            Record("bn_bwd_apply", bn, (g, bn + ".coef"), (dz,), ())]
+
+
+def _msrb_records(p, dpre, virtual, bn_eval=frozenset()):
     """Launches of `_msrb_bwd` for the MSRB with parameter prefix `p`; `virtual`: the block input is relu(bn(z)) of the layer
     below, so the last dgrad's epilogue also leaves that BatchNorm's backward sums."""
     recs = [Record("wgrad", p + "confusion", (dpre,), (), (p + "confusion.weight", p + "confusion.bias"))]
     for o, nm in ((0, "conv_3_2"), (128, "conv_5_2")):
         sl = f"[{o}:{o + 128}]"
         g, dz, bn = p + "g2" + sl, p + "dz2" + sl, p + nm + ".1"
-        recs += [Record("dgrad", p + "confusion" + sl, (dpre,), (g, g + ".sums"), ()),
-                 Record("bn_bwd_finalize", bn, (g + ".sums",), (bn + ".coef",), (bn + ".weight", bn + ".bias")),
-                 Record("bn_bwd_apply", bn, (g, bn + ".coef"), (dz,), ())]
+        recs += [Record("dgrad", p + "confusion" + sl, (dpre,), (g, g + ".sums"), ())]
+        recs += _bn_records(bn, g, dz, (bn + ".weight", bn + ".bias"), bn_eval)
     dz32, dz52 = p + "dz2[0:128]", p + "dz2[128:256]"
     bn1 = p + "conv_3_1.1|conv_5_1.1"
     recs += [
         Record("wgrad", p + "conv_3_2.0", (dz32,), (), (p + "conv_3_2.0.weight", p + "conv_3_2.0.bias")),
         Record("wgrad", p + "conv_5_2.0", (dz52,), (), (p + "conv_5_2.0.weight", p + "conv_5_2.0.bias")),
         Record("dgrad", p + "conv_3_2.0", (dz32,), (p + "g1.3",), ()),
-        Record("dgrad", p + "conv_5_2.0", (dz52, p + "g1.3"), (p + "g1", p + "g1.sums"), ()),
-        Record("bn_bwd_finalize", bn1, (p + "g1.sums",), (bn1 + ".coef",),
-               (p + "conv_3_1.1.weight", p + "conv_3_1.1.bias", p + "conv_5_1.1.weight", p + "conv_5_1.1.bias")),
-        Record("bn_bwd_apply", bn1, (p + "g1", bn1 + ".coef"), (p + "dz1",), ()),
+        Record("dgrad", p + "conv_5_2.0", (dz52, p + "g1.3"), (p + "g1", p + "g1.sums"), ())]
+    recs += _bn_records(bn1, p + "g1", p + "dz1", (p + "conv_3_1.1.weight", p + "conv_3_1.1.bias", p + "conv_5_1.1.weight",
+                                                   p + "conv_5_1.1.bias"), bn_eval)
+    recs += [
         Record("wgrad", p + "conv_3_1.0", (p + "dz1",), (), (p + "conv_3_1.0.weight", p + "conv_3_1.0.bias")),
         Record("wgrad", p + "conv_5_1.0", (p + "dz1",), (), (p + "conv_5_1.0.weight", p + "conv_5_1.0.bias")),
         Record("dgrad", p + "conv_3_1.0", (p + "dz1", dpre), (p + "dx.3",), ()),
@@ -98,22 +121,27 @@ def _msrb_records(p, dpre, virtual):
 def _prune(recs, want, want_out):
     """The records that something wanting a gradient depends on: one of its parameter gradients is in `want`, or one of its
     outputs is in `want_out` or is consumed by a kept record (one sweep from the back: consumers follow producers).  A kept
-    head_bwd whose weight gradient nobody wants becomes head_dgrad (tsr_head_dgrad: the same dz_h0, no weight partials)."""
+    head_bwd whose weight gradient nobody wants becomes head_dgrad (tsr_head_dgrad: the same dz_h0, no weight partials); a
+    kept dgrad whose BatchNorm sums nobody reads (an eval-mode BatchNorm with gamma and beta frozen) loses that output."""
     need, keep = set(want_out), []
     for r in reversed(recs):
         if any(n in want for n in r.params) or any(t in need for t in r.produces):
             need.update(r.consumes)
             if r.kind == "head_bwd" and not any(n in want for n in r.params):
                 r = Record("head_dgrad", r.layer, r.consumes, r.produces, ())
+            if r.kind == "dgrad" and any(t.endswith(".sums") and t not in need for t in r.produces):
+                r = r._replace(produces=tuple(t for t in r.produces if not t.endswith(".sums") or t in need))
             keep.append(r)
     keep.reverse()
     return keep
 
 
-def backward_plan(seqsCnt, n_msrb, n_res, want, want_dx=False):
+def backward_plan(seqsCnt, n_msrb, n_res, want, want_dx=False, bn_eval=frozenset()):
     """Launch list of `TrainEngine.backward` for a TactileSR of `seqsCnt` frames, `n_msrb` MSRBs and `n_res` ResBlocks when
     the parameter gradients named in `want` (and, with `want_dx`, the taxel gradient "LR.grad") are asked for.  `want` = every
-    parameter name gives the unfiltered list: the all-trainable step."""
+    parameter name gives the unfiltered list: the all-trainable step.  `bn_eval`: module paths of the BatchNorm layers that
+    are in eval mode (running statistics held)."""
+    bn_eval = frozenset(bn_eval)
     recs = [Record("head_bwd", "output_layer.2", ("saved:dout",), ("dz_h0",), ("output_layer.2.weight",)),
             Record("wgrad", "output_layer.0", ("dz_h0",), (), ("output_layer.0.weight",)),
             Record("dgrad", "output_layer.0", ("dz_h0",), ("g_hcat[0:64]", "g_hcat[64:128]"), ())]
@@ -127,32 +155,29 @@ def backward_plan(seqsCnt, n_msrb, n_res, want, want_dx=False):
     dpre = "g_hcat[64:128]"
     for i in reversed(range(n_msrb)):
         p = f"patternFeatureExtra_layer.{i}."
-        recs += _msrb_records(p, dpre, virtual=(i == 0))
+        recs += _msrb_records(p, dpre, virtual=(i == 0), bn_eval=bn_eval)
         dpre = p + "dx"
     bn = "inputContact_layer.1"
-    recs += [Record("bn_bwd_finalize", bn, (dpre + ".sums",), (bn + ".coef",), (bn + ".weight", bn + ".bias")),
-             Record("bn_bwd_apply", bn, (dpre, bn + ".coef"), ("dzf",), ()),
-             Record("wgrad", "inputContact_layer.0", ("dzf",), (), ("inputContact_layer.0.weight",))]
+    recs += _bn_records(bn, dpre, "dzf", (bn + ".weight", bn + ".bias"), bn_eval)
+    recs += [Record("wgrad", "inputContact_layer.0", ("dzf",), (), ("inputContact_layer.0.weight",))]
     for t in range(seqsCnt):
         p = f"inputLayer_pattern_list.{t}."
         sl = f"[{64 * t}:{64 * t + 64}]"
         gT, dzT = "gT" + sl, "dzT" + sl
-        recs += [Record("dgrad", "inputContact_layer.0" + sl, ("dzf",), (gT, gT + ".sums"), ()),
-                 Record("bn_bwd_finalize", p + "5", (gT + ".sums",), (p + "5.coef",), (p + "5.weight", p + "5.bias")),
-                 Record("bn_bwd_apply", p + "5", (gT, p + "5.coef"), (dzT,), ()),
-                 Record("wgrad", p + "4", (dzT,), (), (p + "4.weight",)),
-                 Record("dgrad", p + "4", (dzT,), (p + "g1", p + "g1.sums"), ()),
-                 Record("bn_bwd_finalize", p + "2", (p + "g1.sums",), (p + "2.coef",), (p + "2.weight", p + "2.bias")),
-                 Record("bn_bwd_apply", p + "2", (p + "g1", p + "2.coef"), (p + "dz1",), ()),
-                 Record("stem_wgrad", p + "1", (p + "dz1",), (), (p + "1.weight",)),
+        recs += [Record("dgrad", "inputContact_layer.0" + sl, ("dzf",), (gT, gT + ".sums"), ())]
+        recs += _bn_records(p + "5", gT, dzT, (p + "5.weight", p + "5.bias"), bn_eval)
+        recs += [Record("wgrad", p + "4", (dzT,), (), (p + "4.weight",)),
+                 Record("dgrad", p + "4", (dzT,), (p + "g1", p + "g1.sums"), ())]
+        recs += _bn_records(p + "2", p + "g1", p + "dz1", (p + "2.weight", p + "2.bias"), bn_eval)
+        recs += [Record("stem_wgrad", p + "1", (p + "dz1",), (), (p + "1.weight",)),
                  Record("stem_dgrad", p + "1", (p + "dz1",), ("LR.grad",), ())]
     return _prune(recs, frozenset(want), ("LR.grad",) if want_dx else ())
 
 
-def block_backward_plan(kind, want, want_dx=True):
+def block_backward_plan(kind, want, want_dx=True, bn_eval=frozenset()):
     """`backward_plan` for a standalone ``MSRB`` (`kind` "msrb") / ``ResBlock`` ("res"): parameter names carry no prefix, the
     incoming gradient is "saved:dpre" and "dx" is the gradient of the block input."""
-    recs = _msrb_records("", "saved:dpre", virtual=False) if kind == "msrb" else _res_records("", "saved:dpre")
+    recs = _msrb_records("", "saved:dpre", False, frozenset(bn_eval)) if kind == "msrb" else _res_records("", "saved:dpre")
     return _prune(recs, frozenset(want), ("dx",) if want_dx else ())
 
 
@@ -337,6 +362,19 @@ class TrainEngine:
         return vec   # rows: scale, shift, xhat_a, xhat_b
 
     @staticmethod
+    def _bn_eval_vectors(bias, gamma, beta, rm, rv, eps, C):
+        """The 4xC BN vectors of a BatchNorm layer in eval mode (``bn.eval()`` inside the training module): from the running
+        statistics, which stay as they are -- no statistics pass, no num_batches_tracked bump."""
+        vec = torch.empty(4, C, dtype=torch.float32, device=gamma.device)
+        call("tsr_bn_eval_vectors", ptr(bias), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), _F(eps), _I(C),
+             ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(vec[3]), stream())
+        return vec
+
+    def _bn_held_vec(self, conv_bias, bn, C):
+        return self._bn_eval_vectors(conv_bias.detach() if conv_bias is not None else None, bn.weight.detach(),
+                                     bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, C)
+
+    @staticmethod
     def _bump_nbt(c):
         """num_batches_tracked += 1 of every BatchNorm layer the forward ran, as ONE launch (27 one-element launches before)."""
         if c.nbt:
@@ -397,6 +435,7 @@ class TrainEngine:
         wp = torch.empty(_lib.load().tsr_conv_weight_b16k_pair_elems(cin), dtype=torch.bfloat16, device=w.device)
         call("tsr_pack_conv_weight_b16k_pair", ptr(w), ptr(wp), _I(cin), stream())
         with _timed(self.profile, ("fwd", 5, 128, cin)):
+            # (the pair form only knows epi_mode 1: with both layers in eval mode its statistics slab is simply not read)
             conv_ex(B=c.B, H=c.H, W=c.W, src=self._plain(c, X), w=wp, cout=128, ks=5, out=cat1, out_ctot=128, out_coff=0,
                     epi_mode=1, slab=c.slab, slab_cnt=c.slab_cnt, nsplit=NS_B16K_PAIR)
         cat = lambda a, b: torch.cat([a.detach(), b.detach()])
@@ -404,12 +443,21 @@ class TrainEngine:
         rm, rv = cat(b3.running_mean, b5.running_mean), cat(b3.running_var, b5.running_var)
         bias = cat(c3.bias, c5.bias) if c3.bias is not None else None
         gamma, beta = cat(b3.weight, b5.weight), cat(b3.bias, b5.bias)     # (named: a temporary's block would be reused)
+        held = (not b3.training, not b5.training)
+        if any(held):
+            ev = self._bn_eval_vectors(bias, gamma, beta, rm, rv, b3.eps, 128)      # (before the finalize below moves rm / rv)
+            if all(held):
+                return ev
         call("tsr_bn_stats_finalize", ptr(c.slab), ptr(c.slab_cnt), _I(self._entries(c, 128, 5)), _I(128), ptr(bias),
              ptr(gamma), ptr(beta), ptr(rm), ptr(rv), _F(b3.momentum), _F(b3.eps),
              ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(vec[3]), ptr(c.work), stream())
-        b3.running_mean.copy_(rm[:64]); b5.running_mean.copy_(rm[64:])
-        b3.running_var.copy_(rv[:64]); b5.running_var.copy_(rv[64:])
-        c.nbt += [b3.num_batches_tracked, b5.num_batches_tracked]
+        for h, bnm, sl in ((held[0], b3, slice(0, 64)), (held[1], b5, slice(64, 128))):
+            if h:          # a mixed pair: this half keeps its statistics and takes the running-statistics vectors
+                vec[:, sl] = ev[:, sl]
+                continue
+            bnm.running_mean.copy_(rm[sl])
+            bnm.running_var.copy_(rv[sl])
+            c.nbt.append(bnm.num_batches_tracked)
         return vec
 
     def _conv_bn(self, c: _Ctx, src: Act, conv, bn, out, out_ctot, out_coff, out_amax=None):
@@ -420,6 +468,11 @@ class TrainEngine:
             src, wp, wis, ns = self._plain(c, src), self._packw_b16k(conv), None, NS_B16K
         else:
             (wp, wis), ns = self._packw(c, conv), self.nsplit
+        if not bn.training:      # eval-mode BatchNorm: the raw output alone (epi_mode 0, no scale / shift / ReLU), no statistics
+            with _timed(self.profile, ("fwd", ks, cout, cin)):
+                conv_ex(B=c.B, H=c.H, W=c.W, src=src, w=wp, cout=cout, ks=ks, out=out, out_ctot=out_ctot,
+                        out_coff=out_coff, nsplit=ns, w_amax=wis, out_amax=out_amax)
+            return self._bn_held_vec(conv.bias, bn, cout)
         with _timed(self.profile, ("fwd", ks, cout, cin)):
             conv_ex(B=c.B, H=c.H, W=c.W, src=src, w=wp, cout=cout, ks=ks, out=out, out_ctot=out_ctot,
                     out_coff=out_coff, epi_mode=1, slab=c.slab, slab_cnt=c.slab_cnt, nsplit=ns,
@@ -433,6 +486,10 @@ class TrainEngine:
         HW = H * W
         c.B, c.H, c.W, c.HW = B, H, W, HW
         c.nbt = []          # BatchNorm num_batches_tracked counters this forward updates (bumped together: _bump_nbt)
+        # BatchNorm layers in eval mode (nn.BatchNorm2d.eval() inside the training module): running statistics, left alone
+        root = self.m if self.m is not None else self.block
+        c.bn_eval = frozenset(n for n, mod in root.named_modules()
+                              if isinstance(mod, torch.nn.BatchNorm2d) and not mod.training)
         lib = _lib.load()
         c.entries = lib.tsr_conv2d_slab_entries(B, H, W)
         c.st_entries = st_entries = lib.tsr_cb16_stats_entries(B, HW)
@@ -530,9 +587,12 @@ class TrainEngine:
             z1 = buf(64)
             am = new_amax()
             self._stem(x, ctot_in, A * t, A, hin, win, sf, seq[1].weight.detach(), z1, 0, B, am)
-            call("tsr_cb16_stats_b16" if self.io16 else "tsr_cb16_stats", ptr(z1), _I(64), _I(0), _I(B), _I(HW),
-                 ptr(c.slab), ptr(c.slab_cnt), stream())
-            v1 = self._bn_finalize(c, None, seq[2], c.slab, c.slab_cnt, st_entries, 64)
+            if seq[2].training:
+                call("tsr_cb16_stats_b16" if self.io16 else "tsr_cb16_stats", ptr(z1), _I(64), _I(0), _I(B), _I(HW),
+                     ptr(c.slab), ptr(c.slab_cnt), stream())
+                v1 = self._bn_finalize(c, None, seq[2], c.slab, c.slab_cnt, st_entries, 64)
+            else:
+                v1 = self._bn_held_vec(None, seq[2], 64)
             c.z1.append(z1)
             c.bn1.append(v1)
             c.am_z1.append(am)
@@ -705,23 +765,46 @@ class TrainEngine:
         were just produced by the dgrad epilogue over the same C channels).  `gnames` = (weight, bias) parameter names:
         the wanted ones of dgamma / dbeta are then written straight into their gradient slots (no copy launches).
         Plan records ("bn_bwd_finalize", layer) -- needed for dgamma / dbeta or for the apply pass -- and
-        ("bn_bwd_apply", layer), which turns g into dz in place and runs only when dz is consumed."""
-        if ("bn_bwd_finalize", layer) not in c.live:
+        ("bn_bwd_apply", layer), which turns g into dz in place and runs only when dz is consumed.
+        A layer in eval mode (`c.bn_eval`): dz = scale * g -- one pass over g alone (tsr_bn_bwd_apply_eval), and the finalize
+        (tsr_bn_bwd_finalize_eval: dgamma, dbeta only) runs just when one of the two is wanted."""
+        finalize = ("bn_bwd_finalize", layer) in c.live
+        held = bn_held(layer, c.bn_eval)
+        if not finalize and not (held and ("bn_bwd_apply", layer) in c.live):
             return None
         dev = g_buf.device
         out = torch.empty(5, C, dtype=torch.float32, device=dev)
         gnames = tuple(n if n in c.want else None for n in gnames) if gnames else (None, None)
         dg = grads.dest(gnames[0], (C,)) if gnames[0] else out[0]
         db = grads.dest(gnames[1], (C,)) if gnames[1] else out[1]
-        call("tsr_bn_bwd_finalize", ptr(c.slab), _I(c.last_entries), _I(C), _D(float(c.B * c.HW)),
-             ptr(bn_vec[0]), ptr(bn_vec[2]), ptr(bn_vec[3]), ptr(dg), ptr(db), ptr(out[2]), ptr(out[3]),
-             ptr(out[4]), ptr(c.work), stream())
-        if gnames[0]:
+        if held:
+            if finalize:
+                call("tsr_bn_bwd_finalize_eval", ptr(c.slab), _I(c.last_entries), _I(C), ptr(dg), ptr(db), ptr(c.work),
+                     stream())
+        else:
+            call("tsr_bn_bwd_finalize", ptr(c.slab), _I(c.last_entries), _I(C), _D(float(c.B * c.HW)),
+                 ptr(bn_vec[0]), ptr(bn_vec[2]), ptr(bn_vec[3]), ptr(dg), ptr(db), ptr(out[2]), ptr(out[3]),
+                 ptr(out[4]), ptr(c.work), stream())
+            # layers that share this launch, one of them in eval mode (a mixed stage-1 pair): dgamma / dbeta are the same sums
+            # in both modes and c1 = scale already; without the batch-statistics terms its channels get dz = scale * g
+            for k, n in enumerate(bn_members(layer)):
+                if n in c.bn_eval:
+                    w = C // len(bn_members(layer))
+                    out[3:5, k * w:(k + 1) * w].zero_()
+        if finalize and gnames[0]:
             grads.put(gnames[0], dg)
-        if gnames[1]:
+        if finalize and gnames[1]:
             grads.put(gnames[1], db)
         if ("bn_bwd_apply", layer) not in c.live:
-            return out
+            return out if finalize else None
+        if held:
+            if self.io16:
+                call("tsr_bn_bwd_apply_eval_b16", ptr(g_buf), _I(g_ctot), _I(g_coff), ptr(bn_vec[0]), _I(C), _I(c.B),
+                     _I(c.HW), stream())
+            else:
+                call("tsr_bn_bwd_apply_eval", ptr(g_buf), _I(g_ctot), _I(g_coff), ptr(bn_vec[0]), _I(C), _I(c.B), _I(c.HW),
+                     ptr(out_amax), stream())
+            return out if finalize else None
         if self.io16:
             call("tsr_bn_bwd_apply_b16", ptr(g_buf), _I(g_ctot), _I(g_coff), ptr(z.buf), _I(z.ctot), _I(z.coff + zoff),
                  ptr(out[2]), ptr(out[3]), ptr(out[4]), _I(C), _I(c.B), _I(c.HW), stream())
@@ -751,12 +834,14 @@ class TrainEngine:
         self._dgrad(c, D1, rb.conv1, 0, 64, d0, 64, 0, res=dpre, mask=s.X if mask_input else None, out_amax=am)
         return Act(d0, 64, 0, 64, amax=am)
 
-    def _msrb_bwd(self, c, s, blk, name, dpre: Act, grads, new_amax, buf, tag="msrb", mask_input=True):
+    def _msrb_bwd(self, c, s, blk, name, dpre: Act, grads, new_amax, buf, tag="msrb", mask_input=True, in_bn=None):
         """Backward of one MSRB.  `dpre` = gradient w.r.t. the block output BEFORE its ReLU; returns the gradient w.r.t.
         the block input (None when the backward plan has no launch producing it): masked by the input's ReLU pattern / with
-        the BatchNorm-backward sums of a virtual input (`mask_input`, the chained engine) or plain (standalone module)."""
+        the BatchNorm-backward sums of a virtual input (`mask_input`, the chained engine; `in_bn`: that BatchNorm's path) or
+        plain (standalone module)."""
         name = name + "." if name else ""          # (standalone module: parameter names carry no prefix)
         on = lambda kind, layer: (kind, name + layer) in c.live
+        sums = lambda layer: on("bn_bwd_finalize", layer)      # whether the dgrad in front of this BatchNorm leaves its sums
         # confusion 1x1: a = relu(bn(cat2)), dz = dpre
         self._wgrad(c, s.A2, dpre, blk.confusion, grads, name + "confusion", True)
         if not (on("dgrad", "confusion[0:128]") or on("dgrad", "confusion[128:256]")):
@@ -770,7 +855,7 @@ class TrainEngine:
                 continue
             mk = Act(s.cat2, 256, o, 128, s.bn_c2[0, o:o + 128], s.bn_c2[1, o:o + 128], s.bn_c2[2, o:o + 128],
                      s.bn_c2[3, o:o + 128])
-            self._dgrad(c, dpre, blk.confusion, o, 128, g2, 256, o, mask=mk, bn=True)
+            self._dgrad(c, dpre, blk.confusion, o, 128, g2, 256, o, mask=mk, bn=sums(nm + ".1"))
             self._bn_bwd(c, f"{name}{nm}.1", g2, 256, o, Act(s.cat2, 256, 0, 256), o, 128, s.bn_c2[:, o:o + 128], bnm, grads,
                          nm, out_amax=am_g2[half], gnames=(f"{name}{nm}.1.weight", f"{name}{nm}.1.bias"))
         if self.debug is not None:
@@ -783,14 +868,15 @@ class TrainEngine:
         g1 = buf(128)
         self._dgrad(c, DZ32, blk.conv_3_2[0], 0, 128, g1, 128, 0)
         mk = Act(s.cat1, 128, 0, 128, s.bn_c1[0], s.bn_c1[1], s.bn_c1[2], s.bn_c1[3])
-        self._dgrad(c, DZ52, blk.conv_5_2[0], 0, 128, g1, 128, 0, res=Act(g1, 128, 0, 128), mask=mk, bn=True)
+        self._dgrad(c, DZ52, blk.conv_5_2[0], 0, 128, g1, 128, 0, res=Act(g1, 128, 0, 128), mask=mk,
+                    bn=sums("conv_3_1.1|conv_5_1.1"))
         am_g1 = new_amax()
         r = self._bn_bwd(c, f"{name}conv_3_1.1|conv_5_1.1", g1, 128, 0, Act(s.cat1, 128, 0, 128), 0, 128, s.bn_c1, None,
                          grads, "", out_amax=am_g1)
-        for gname, row in ((f"{name}conv_3_1.1.weight", r[0, :64]), (f"{name}conv_3_1.1.bias", r[1, :64]),
-                           (f"{name}conv_5_1.1.weight", r[0, 64:]), (f"{name}conv_5_1.1.bias", r[1, 64:])):
+        for gname, row, lo in ((f"{name}conv_3_1.1.weight", 0, 0), (f"{name}conv_3_1.1.bias", 1, 0),
+                               (f"{name}conv_5_1.1.weight", 0, 64), (f"{name}conv_5_1.1.bias", 1, 64)):
             if gname in c.want:
-                grads.put_copy(gname, row)
+                grads.put_copy(gname, r[row, lo:lo + 64])
         del g2
         if self.debug is not None:
             self.debug[f"{tag}.dz1"] = g1.clone()
@@ -804,7 +890,8 @@ class TrainEngine:
         virtual = mask_input and s.X.scale is not None
         am = new_amax()
         self._dgrad(c, DZ51, blk.conv_5_1[0], 0, 64, dx, 64, 0, res=Act(dx, 64, 0, 64),
-                    mask=s.X if mask_input else None, bn=virtual, out_amax=None if virtual else am)
+                    mask=s.X if mask_input else None, bn=virtual and ("bn_bwd_finalize", in_bn) in c.live,
+                    out_amax=None if virtual else am)
         return Act(dx, 64, 0, 64, amax=am)
 
     # ------------------------------------------------------------------ backward
@@ -819,7 +906,7 @@ class TrainEngine:
         from ..ddp import GradSink
         T = m.seqsCnt
         # the launches something that wants a gradient depends on (all of today's list when every parameter is trainable)
-        c.live = {r.key for r in backward_plan(T, len(c.blocks), len(c.res), c.want, c.want_dx)}
+        c.live = {r.key for r in backward_plan(T, len(c.blocks), len(c.res), c.want, c.want_dx, c.bn_eval)}
         on = lambda kind, layer: (kind, layer) in c.live
         grads = GradSink(self, dict(m.named_parameters()), dev, token=c, want=c.want)
 
@@ -892,7 +979,7 @@ class TrainEngine:
         for i in reversed(range(len(c.blocks))):
             if dpre is not None:
                 dpre = self._msrb_bwd(c, c.blocks[i], m.patternFeatureExtra_layer[i], f"patternFeatureExtra_layer.{i}", dpre,
-                                      grads, new_amax, buf, tag=f"msrb{i}")
+                                      grads, new_amax, buf, tag=f"msrb{i}", in_bn="inputContact_layer.1")
         if dpre is None:          # nothing at or below the first MSRB's input wants a gradient
             return grads.finalize()
         # X of block 0 is the fuse conv's relu(bn(zf)): finish its BN backward -> dzf
@@ -908,7 +995,7 @@ class TrainEngine:
                 continue
             mk = Act(c.catT, 64 * T, o, 64, c.bn2[0, o:o + 64], c.bn2[1, o:o + 64], c.bn2[2, o:o + 64],
                      c.bn2[3, o:o + 64])
-            self._dgrad(c, dpre, m.inputContact_layer[0], o, 64, gT, 64 * T, o, mask=mk, bn=True)
+            self._dgrad(c, dpre, m.inputContact_layer[0], o, 64, gT, 64 * T, o, mask=mk, bn=on("bn_bwd_finalize", name + ".5"))
             am_gT = new_amax()
             self._bn_bwd(c, name + ".5", gT, 64 * T, o, Act(c.catT, 64 * T, 0, 64 * T), o, 64, c.bn2[:, o:o + 64], None, grads,
                          "", out_amax=am_gT, gnames=(name + ".5.weight", name + ".5.bias"))
@@ -919,7 +1006,7 @@ class TrainEngine:
             if not on("dgrad", name + ".4"):
                 continue
             g1 = buf(64)
-            self._dgrad(c, DZ2, seq[4], 0, 64, g1, 64, 0, mask=A1, bn=True)
+            self._dgrad(c, DZ2, seq[4], 0, 64, g1, 64, 0, mask=A1, bn=on("bn_bwd_finalize", name + ".2"))
             self._bn_bwd(c, name + ".2", g1, 64, 0, Act(c.z1[t], 64, 0, 64), 0, 64, v1, None, grads, "",
                          gnames=(name + ".2.weight", name + ".2.bias"))
             if on("stem_wgrad", name + ".1"):
@@ -1016,7 +1103,7 @@ class BlockEngine(TrainEngine):
         from ..ddp import GradSink
         dev = dout.device
         B, H, W = c.B, c.H, c.W
-        c.live = {r.key for r in block_backward_plan(self.kind, c.want, c.want_dx)}
+        c.live = {r.key for r in block_backward_plan(self.kind, c.want, c.want_dx, c.bn_eval)}
         grads = GradSink(self, dict(self.block.named_parameters()), dev, token=c, want=c.want)
         if not c.live:
             return None, grads.finalize()

@@ -39,6 +39,34 @@ def _reference_init(root: nn.Module) -> None:
             nn.init.constant_(m.bias, 0.1)
 
 
+_HOLD = "_tsr_hold_bn_prev"      # on a marked nn.BatchNorm2d: the `training` flag it had when it was marked
+
+
+def hold_bn_statistics(module: nn.Module, hold: bool = True) -> nn.Module:
+    """Fine-tune on fixed statistics: put every ``nn.BatchNorm2d`` under `module` in eval mode and MARK it, so that the
+    ``train()`` of ``TactileSR`` / ``MSRB`` / ``ResBlock`` (a trainer's per-epoch ``model.train()``) does not undo it.  The
+    train step then normalises those layers with their running statistics, leaves ``running_mean`` / ``running_var`` /
+    ``num_batches_tracked`` alone and runs the eval-mode backward (torch's ``bn.eval()`` inside a training module; a plain
+    ``bn.eval()`` without the mark is honoured the same way until the next ``train()``).  ``hold=False`` clears the mark and
+    restores the mode the layer had when it was marked.  No parameter, buffer or ``state_dict`` key changes."""
+    for m in module.modules():
+        if isinstance(m, nn.BatchNorm2d):
+            if hold:
+                if not hasattr(m, _HOLD):
+                    setattr(m, _HOLD, m.training)
+                m.training = False
+            elif hasattr(m, _HOLD):
+                m.training = getattr(m, _HOLD)
+                delattr(m, _HOLD)
+    return module
+
+
+def _reapply_hold(root: nn.Module) -> None:
+    for m in root.modules():
+        if isinstance(m, nn.BatchNorm2d) and hasattr(m, _HOLD):
+            m.training = False
+
+
 class _StandaloneBlock(nn.Module):
     """Shared forward of the standalone ``MSRB`` / ``ResBlock`` modules (the whole-network engine of ``TactileSR`` runs
     the same kernels on its own buffers): ``block(x)`` with x ``(B, 64, H, W)`` fp32 NCHW on a ROCm device.  Eval mode
@@ -55,6 +83,11 @@ class _StandaloneBlock(nn.Module):
 
     def extra_repr(self):
         return f"arithmetic: eval conv_impl={self.conv_impl!r}, train_impl={self.train_impl!r}"
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        _reapply_hold(self)          # hold_bn_statistics: marked BatchNorm layers stay in eval mode
+        return self
 
     def _param_key(self):
         return (self.conv_impl, _lib.param_epoch()) + tuple((t.data_ptr(), t._version)
@@ -522,6 +555,11 @@ class TactileSR(nn.Module):
 
     def _init_network(self):
         _reference_init(self)
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        _reapply_hold(self)          # hold_bn_statistics: marked BatchNorm layers stay in eval mode
+        return self
 
     # ------------------------------------------------------------------ engine
     def _param_key(self):

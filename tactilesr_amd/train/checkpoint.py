@@ -101,7 +101,7 @@ def load_checkpoint(path: str, model, optimizer=None, lr_scheduler=None, num_gpu
     return ck
 
 
-def model_param_init(seqs_model, single_frame_state_dict, make_single_model, freeze=False):
+def model_param_init(seqs_model, single_frame_state_dict, make_single_model, freeze=False, hold_bn=False):
     """The Seqs trainer's weight transplant (train/tactileSRSeqs_train.py:43-59): build the single-frame
     model, load its checkpointed weights, and REPLACE the two feature-extraction submodules of the
     multi-frame model by it.  As in the reference, an optimizer created before this call keeps pointing at
@@ -113,7 +113,10 @@ def model_param_init(seqs_model, single_frame_state_dict, make_single_model, fre
     two transplanted containers: the train step then skips every backward launch that only served them and those
     gradients do not exist, so they are no part of a clipping norm either (the norm is over the parameters that
     train); the fused clip applies and ``GraphedTrainStep(clip_grad_norm>0)`` accepts the flow.  The BatchNorm layers of
-    the frozen blocks stay in batch-statistics mode either way."""
+    the frozen blocks stay in batch-statistics mode unless ``hold_bn=True``: that applies ``hold_bn_statistics`` to the two
+    transplanted containers -- their BatchNorm layers normalise with the single-frame running statistics, which the Seqs
+    batches then no longer rewrite, and (with ``freeze=True``) the step runs no statistics launch for them in forward and
+    one scale pass per BatchNorm tensor in backward.  ``hold_bn=False`` (default) keeps the reference's behaviour."""
     single = make_single_model()
     single.load_state_dict(single_frame_state_dict, strict=False)
     single = single.to(next(seqs_model.parameters()).device)
@@ -123,4 +126,8 @@ def model_param_init(seqs_model, single_frame_state_dict, make_single_model, fre
         for container in (seqs_model.patternFeatureExtra_layer, seqs_model.forceFeatureExtra_layer):
             for p in container.parameters():
                 p.requires_grad_(False)
+    if hold_bn:
+        from ..model.tactileSR_model import hold_bn_statistics
+        for container in (seqs_model.patternFeatureExtra_layer, seqs_model.forceFeatureExtra_layer):
+            hold_bn_statistics(container)
     return seqs_model

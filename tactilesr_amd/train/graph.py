@@ -18,7 +18,8 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
   (an lr scheduler works unchanged) and the advanced ``state["step"]``.  The step then has the eager step's results
   bit for bit, checkpoints included.
 * Recapture: when ``train_impl``, the parameter / buffer / optimizer-state / gradient-arena addresses, the set of
-  parameters that require grad (the captured backward holds only the launches a trainable parameter depends on), the loss
+  parameters that require grad (the captured backward holds only the launches a trainable parameter depends on), the set
+  of BatchNorm layers in eval mode (``hold_bn_statistics``: their statistics launches are not in the capture), the loss
   config, the optimizer's baked constants (``betas``, ``eps``, ``weight_decay``) or ``clip_grad_norm`` change, the
   graph is dropped and the next ``warmup`` calls run eagerly again before a new capture.  ``captures`` counts the captures.
 * The returned ``total_loss`` is the graph's static OUTPUT BUFFER (like ``GraphedForward``): the next call overwrites
@@ -95,7 +96,8 @@ class GraphedTrainStep:
         return (m.train_impl, id(arena), arena.flat.data_ptr() if arena is not None else 0,
                 tuple(t.data_ptr() for t in m.parameters()), tuple(b.data_ptr() for b in m.buffers()), groups,
                 tuple(self.config[k] for k in _CONFIG_KEYS), self.clip_grad_norm,
-                tuple(p.requires_grad for p in m.parameters()))      # the captured backward holds the trainable set's launches
+                tuple(p.requires_grad for p in m.parameters()),      # the captured backward holds the trainable set's launches
+                tuple(mod.training for mod in m.modules() if isinstance(mod, torch.nn.BatchNorm2d)))      # and each BatchNorm's mode
 
     def _check(self, LR, HR) -> None:
         m = self.model
