@@ -552,6 +552,27 @@ int tpsf_forward(const float* depth, const float* alpha_beta, float* HR, float* 
  * leaves d_alpha_beta and work untouched. */
 int tpsf_backward(const float* depth, const float* alpha_beta, const float* HR, const float* dLR_deg,
                   float* d_alpha_beta, float* work, int B, void* stream);
+/* The full backward of tpsf_forward: upstream gradients of all three outputs -- dLR_deg (B,16), dHR (B,100,100), dpsf
+ * (B,99,99), each optional (NULL = none) -- to d_alpha_beta (B,3) and, when d_depth is not NULL, to the depth (B,100,100).
+ * Per sample, with D the depth, G[i][j] = g(i-j), g(t) = exp(-Kp t^2 / beta^2) for |t| <= 49 and 0 beyond, Kp = 100/4802, H the
+ * Toeplitz matrix of t^2 g(t), P the plateau D > max D - 1e-3 and m_ac(gamma) the normalised pooling mask of taxel (a,c):
+ *     W         = [not P] (dHR + 1e-4 sum_ac dLR_deg[a][c] m_ac(gamma))        (what `work` receives; exactly 0 on the plateau)
+ *     d/dalpha  = sum W (G D G) + sum dpsf g(u) g(v)                           (the first sum over the stored HR / alpha)
+ *     d/dbeta   = alpha (2 Kp / beta^3) (<W, H D G + G D H> + sum dpsf g(u) g(v) (u^2 + v^2))      (u, v from the psf centre)
+ *     d/dgamma  = through dLR_deg only: bit for bit tpsf_backward's for the same dLR_deg, an exact 0 without one
+ *     d_depth   = alpha G W G             (g is even: the adjoint of the "same" convolution is the same Toeplitz pair)
+ * NOT differentiated, as in the reference's autograd: the plateau threshold max D, and the fill value (a detached constant), so
+ * plateau pixels of the OUTPUT take no gradient (whatever dHR holds there is ignored) while the INPUT pixels under the plateau
+ * do receive their d_depth.  An all-plateau image has d_depth exactly 0 and only the psf terms in d/dalpha, d/dbeta.  With dpsf
+ * alone W is 0: d_depth is exactly 0 and `work` is not written.  Samples are independent (NaN / Inf stay in their sample).
+ * With dHR, dpsf and d_depth all NULL this is tpsf_backward: the same two launches, d_alpha_beta and work bit for bit.
+ * Refusals: a NULL depth, alpha_beta, HR, d_alpha_beta or work, all three upstream pointers NULL, or B <= 0, returns status 1,
+ * launches nothing and leaves d_alpha_beta, d_depth and work untouched. */
+int tpsf_backward_ex(const float* depth, const float* alpha_beta, const float* HR,
+                     const float* dLR_deg /* B*16, NULL = none */, const float* dHR /* B*100*100, NULL = none */,
+                     const float* dpsf /* B*99*99, NULL = none */,
+                     float* d_alpha_beta, float* d_depth /* B*100*100, NULL = not wanted */,
+                     float* work, int B, void* stream);
 /* C[i][j] = act(sum_k A(i,k)B(k,j) + bias[j]), A(i,k)=A[i*sa0+k*sa1], B(k,j)=B[k*sb0+j*sb1]; act 0 none,
  * 1 ReLU, 2 Softplus: the nn.Linear layers of MLP_layer (:26-36) and their backward GEMMs.
  * Refusals (the whole family: tsr_sgemm, tsr_sgemm_masked, tsr_sgemm_splitk, tsr_sgemm_splitk_strided, tsr_colsum_splitk): a

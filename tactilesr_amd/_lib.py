@@ -96,6 +96,7 @@ SIGNATURES = {
     "tsr_psnr_ssim": [_P, _P, _I, _I, c_double, c_double, c_double, c_double, _P, _P, _P],
     "tpsf_forward": [_P, _P, _P, _P, _P, _I, _P],
     "tpsf_backward": [_P, _P, _P, _P, _P, _P, _I, _P],
+    "tpsf_backward_ex": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "tsr_sgemm": [_P, _L, _L, _P, _L, _L, _P, _P, _I, _I, _I, _I, _P],
     "tsr_sgemm_splitk": [_P, _L, _L, _P, _L, _L, _P, _I, _I, _I, _I, _P],
     "tsr_sgemm_masked": [_P, _L, _L, _P, _L, _L, _P, _P, _I, _I, _I, _P],

@@ -421,9 +421,19 @@ __global__ __launch_bounds__(256, TPSF_FWD_OCC) void tpsf_fwd_mfma_kernel(const 
 //     column GEMM ahead of their use and held in registers unspilled -- loaded row by row inside the reduction each of
 //     the 2 x 16 weight rows per sample paid a full memory round trip (waves parked 71 % of their cycles): 0.76 -> 0.51 ms
 //     per 8192 samples (the kernel had measured the same at one and at two workgroups per CU before).
+//
+// tpsf_backward_ex adds the other upstream gradients and the depth gradient around the same two kernels:
+//   - an upstream dL/dHR (HAS_DHR) is one more term of wgt off the plateau (the plateau of the OUTPUT is a detached constant),
+//     and dLRd may be absent (HAS_DL = false: no pooling sums at all, d/d(gamma) is an exact 0).  Both are compile-time:
+//     <true, false> is the code tpsf_backward has always run;
+//   - tpsf_bwd_psf_kernel adds the psf output's term of d/d(alpha) and d/d(beta) (or stores it, when it is the only one);
+//   - tpsf_bwd_depth_kernel is the forward's GEMM pair applied to wgt: d loss / d depth = alpha G wgt G.
+template <bool HAS_DL, bool HAS_DHR>
 __global__ __launch_bounds__(256) void tpsf_bwd_pool_kernel(const float* __restrict__ depth, const float* __restrict__ ab,
                                                             const float* __restrict__ HR, const float* __restrict__ dLRd,
+                                                            const float* __restrict__ dHR,
                                                             float* __restrict__ dab, float* __restrict__ wgt, int B) {
+  static_assert(HAS_DL || HAS_DHR, "nothing to reduce");
   __shared__ float ea[400], ea2[400], qd[400];       // [4][100]: mask factors, (x-cx)^2 times them, sum_c dl[a][c] ea_c(x)
   __shared__ float dl[16];
   __shared__ float redf[8];
@@ -436,6 +446,7 @@ __global__ __launch_bounds__(256) void tpsf_bwd_pool_kernel(const float* __restr
     const float k0 = 1e-4f / (1.0f - mn);
     const float* dp = depth + (size_t)b * NPIX;
     const float* hp = HR + (size_t)b * NPIX;
+    const float* gp = HAS_DHR ? dHR + (size_t)b * NPIX : nullptr;
     float mx = -INFINITY;                // pass 1: the plateau threshold (the rows are re-read from L2 in pass 2)
     {
       const f32x4* dp4 = (const f32x4*)dp;             // 40,000 B per sample: 16-B aligned; 2,500 quads, 10 per thread
@@ -447,27 +458,31 @@ __global__ __launch_bounds__(256) void tpsf_bwd_pool_kernel(const float* __restr
         mx = fmaxf(mx, q < NPIX / 4 ? m4 : -INFINITY);
       }
     }
-    for (int i = tid; i < 400; i += 256) {
-      const int a = i / 100, x = i - a * 100;
-      const float t = (float)(x - (12 + 25 * a));
-      const float e = expf(-cm * t * t);
-      ea[i] = e;
-      ea2[i] = t * t * e;
+    if constexpr (HAS_DL) {
+      for (int i = tid; i < 400; i += 256) {
+        const int a = i / 100, x = i - a * 100;
+        const float t = (float)(x - (12 + 25 * a));
+        const float e = expf(-cm * t * t);
+        ea[i] = e;
+        ea2[i] = t * t * e;
+      }
+      if (tid < 16) dl[tid] = dLRd[b * 16 + tid];
     }
-    if (tid < 16) dl[tid] = dLRd[b * 16 + tid];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     if (lane == 0) redf[w] = mx;
     __syncthreads();                                                       // (1) ea, dl, max partials
     const float thr = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3])) - 1e-3f;
-    for (int i = tid; i < 400; i += 256) {
-      const int a = i / 100, x = i - a * 100;
-      qd[i] = dl[a * 4 + 0] * ea[x] + dl[a * 4 + 1] * ea[100 + x] + dl[a * 4 + 2] * ea[200 + x] + dl[a * 4 + 3] * ea[300 + x];
-    }
     float dlsum = 0.f;
+    if constexpr (HAS_DL) {
+      for (int i = tid; i < 400; i += 256) {
+        const int a = i / 100, x = i - a * 100;
+        qd[i] = dl[a * 4 + 0] * ea[x] + dl[a * 4 + 1] * ea[100 + x] + dl[a * 4 + 2] * ea[200 + x] + dl[a * 4 + 3] * ea[300 + x];
+      }
 #pragma unroll
-    for (int t = 0; t < 16; ++t) dlsum += dl[t];
-    __syncthreads();                                                       // (2) qd
+      for (int t = 0; t < 16; ++t) dlsum += dl[t];
+      __syncthreads();                                                     // (2) qd
+    }
     float S[4][4], Sd[4][4], s0 = 0.f, da = 0.f;
 #pragma unroll
     for (int a = 0; a < 4; ++a)
@@ -478,27 +493,50 @@ __global__ __launch_bounds__(256) void tpsf_bwd_pool_kernel(const float* __restr
     for (int k = 0; k < 40; ++k) {
       const int p = tid + 256 * k;
       if (p < NPIX) {
-        const int y = (int)(((unsigned)p * 5243u) >> 19), x = p - y * HS;      // p / 100 for p < 43,698
         const float v = hp[p];                                   // stored HR: the plateau already holds its fill value
-        const float ey[4] = {ea[y], ea[100 + y], ea[200 + y], ea[300 + y]};
-        const float ey2[4] = {ea2[y], ea2[100 + y], ea2[200 + y], ea2[300 + y]};
-        const float ex[4] = {ea[x], ea[100 + x], ea[200 + x], ea[300 + x]};
-        const float ex2[4] = {ea2[x], ea2[100 + x], ea2[200 + x], ea2[300 + x]};
-        const float gsum = ey[0] * qd[x] + ey[1] * qd[100 + x] + ey[2] * qd[200 + x] + ey[3] * qd[300 + x];
-        const float wv = dp[p] > thr ? 0.f : k0 * (gsum - mn * dlsum);
-        wp[p] = wv;
-        s0 += v;
-        da = fmaf(wv, v, da);
+        if constexpr (HAS_DL) {
+          const int y = (int)(((unsigned)p * 5243u) >> 19), x = p - y * HS;      // p / 100 for p < 43,698
+          const float ey[4] = {ea[y], ea[100 + y], ea[200 + y], ea[300 + y]};
+          const float ey2[4] = {ea2[y], ea2[100 + y], ea2[200 + y], ea2[300 + y]};
+          const float ex[4] = {ea[x], ea[100 + x], ea[200 + x], ea[300 + x]};
+          const float ex2[4] = {ea2[x], ea2[100 + x], ea2[200 + x], ea2[300 + x]};
+          const float gsum = ey[0] * qd[x] + ey[1] * qd[100 + x] + ey[2] * qd[200 + x] + ey[3] * qd[300 + x];
+          float wv;
+          if constexpr (HAS_DHR) wv = dp[p] > thr ? 0.f : k0 * (gsum - mn * dlsum) + gp[p];
+          else wv = dp[p] > thr ? 0.f : k0 * (gsum - mn * dlsum);
+          wp[p] = wv;
+          s0 += v;
+          da = fmaf(wv, v, da);
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          const float t = v * ey[a], t2 = v * ey2[a];
+          for (int a = 0; a < 4; ++a) {
+            const float t = v * ey[a], t2 = v * ey2[a];
 #pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            S[a][c] = fmaf(t, ex[c], S[a][c]);
-            Sd[a][c] = fmaf(t2, ex[c], fmaf(t, ex2[c], Sd[a][c]));
+            for (int c = 0; c < 4; ++c) {
+              S[a][c] = fmaf(t, ex[c], S[a][c]);
+              Sd[a][c] = fmaf(t2, ex[c], fmaf(t, ex2[c], Sd[a][c]));
+            }
           }
+        } else {
+          const float wv = dp[p] > thr ? 0.f : gp[p];            // a select: whatever dHR holds on the plateau is dropped
+          wp[p] = wv;
+          da = fmaf(wv, v, da);
         }
       }
+    }
+    if constexpr (!HAS_DL) {
+      // ---- d/d(alpha) alone: no pooling sums, d/d(gamma) is an exact 0
+      double v = (double)da;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      if (lane == 0) redd[w] = v;
+      __syncthreads();                                                     // (3) wave sums
+      if (tid == 0) {
+        const double DA = (redd[0] + redd[1]) + (redd[2] + redd[3]);
+        dab[b * 3 + 0] = (float)(DA / (double)alpha);
+        dab[b * 3 + 2] = 0.f;
+      }
+      __syncthreads();                                                     // (4) LDS free for the next sample
+      continue;
     }
     // ---- block reduction of the 34 partial sums in double (per-thread fp32 sums hold <= 40 terms)
     double vals[34];
@@ -725,6 +763,161 @@ __global__ __launch_bounds__(256, TPSF_BWD_OCC) void tpsf_bwd_dhb_kernel(const f
   }
 }
 
+// The psf output's term of d/d(alpha) and d/d(beta), given dL/dpsf (B,99,99):  psf[u][v] = alpha g(u) g(v), so
+//     d/d(alpha) = sum dpsf g(u) g(v),     d/d(beta) = alpha (2 Kp / beta^3) sum dpsf g(u) g(v) (u^2 + v^2)   (u, v from the centre)
+// psf is regenerated from (alpha, beta) in its separable form (never re-read), the sums are accumulated in double.  ADD: the
+// two sums are added to what tpsf_bwd_pool_kernel / tpsf_bwd_dhb_kernel left in dab (same stream, after them; one thread per
+// sample, no atomics); otherwise they are stored and d/d(gamma) is an exact 0 (dpsf is the only upstream gradient).
+template <bool ADD>
+__global__ __launch_bounds__(256) void tpsf_bwd_psf_kernel(const float* __restrict__ ab, const float* __restrict__ dpsf,
+                                                           float* __restrict__ dab, int B) {
+  __shared__ float g[128];
+  __shared__ double redd[8];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const float alpha = ab[b * 3 + 0], beta = ab[b * 3 + 1];
+    const float cpsf = KP / (beta * beta);
+    for (int i = tid; i < PS; i += 256) { const float t = (float)(i - 49); g[i] = expf(-cpsf * t * t); }
+    __syncthreads();                                                       // (1) g
+    const float* gp = dpsf + (size_t)b * PS * PS;
+    double sa = 0.0, sb = 0.0;
+#pragma unroll 2
+    for (int k = 0; k < 39; ++k) {                                         // 9,801 elements, 256 per pass
+      const int p = tid + 256 * k;
+      if (p < PS * PS) {
+        const int u = p / PS, v = p - u * PS;
+        const float guv = g[u] * g[v];
+        const int r2 = (u - 49) * (u - 49) + (v - 49) * (v - 49);
+        const double t = (double)gp[p] * (double)guv;
+        sa += t;
+        sb += t * (double)r2;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      sa += __shfl_xor(sa, o);
+      sb += __shfl_xor(sb, o);
+    }
+    if (lane == 0) { redd[w] = sa; redd[4 + w] = sb; }
+    __syncthreads();                                                       // (2) wave sums
+    if (tid == 0) {
+      const double SA = (redd[0] + redd[1]) + (redd[2] + redd[3]);
+      const double SB = (redd[4] + redd[5]) + (redd[6] + redd[7]);
+      const float da = (float)SA;
+      const float db = (float)(SB * (double)alpha * 2.0 * (double)KP / ((double)beta * beta * beta));
+      if (ADD) {
+        dab[b * 3 + 0] += da;
+        dab[b * 3 + 1] += db;
+      } else {
+        dab[b * 3 + 0] = da;
+        dab[b * 3 + 1] = db;
+        dab[b * 3 + 2] = 0.f;
+      }
+    }
+    __syncthreads();                                                       // (3) LDS free for the next sample
+  }
+}
+
+// d loss / d depth = alpha G W G, W = the per-pixel dL/dHR tpsf_bwd_pool_kernel left in the work buffer (0 on the plateau
+// of the OUTPUT; the input pixels under the plateau do receive a gradient; the threshold depth.max() is not differentiated).
+// g is even, so the adjoint of the "same" convolution is the same Toeplitz pair: this is the forward kernel's GEMM pair --
+// rows of W from global memory into registers, R = W G, R^T planes to LDS, G R -- in the same two-plane fp16 arithmetic
+// with the scales taken from max|W| of the sample (1 for an all-zero W: exact zeros out), and a plain store behind it: no
+// plateau fill, no pooling, no psf.  Persistent over the batch like the forward, the next sample's rows fetched under the
+// column GEMM's tail.  Everything a sample leaves in LDS is rewritten by the next one: NaN / Inf stay in their sample.
+__global__ __launch_bounds__(256, TPSF_FWD_OCC) void tpsf_bwd_depth_kernel(const float* __restrict__ wgt,
+                                                                           const float* __restrict__ ab,
+                                                                           float* __restrict__ dd, int B) {
+  __shared__ __attribute__((aligned(16))) char Tc[2 * T_PLANE];
+  __shared__ __attribute__((aligned(16))) char RT[2 * RT_PLANE + 16];
+  __shared__ float g[128];
+  __shared__ float red[4];
+
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, li = lane & 31;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (tid < 4) ((float*)(RT + 2 * RT_PLANE))[tid] = 0.f;
+  const int y = 32 * w + li;
+  const int q8 = (li + 7) & ~7, rcopy = q8 - li;
+  const int laneT = rcopy * TC_STRIDE + 2 * (T_OFF + 8 * h - q8);
+
+  f32x4 wA[7][2];
+  auto load_rows = [&](int b) {
+    const float* p = wgt + (size_t)b * NPIX + y * HS + 8 * h;
+#pragma unroll
+    for (int ks = 0; ks < 7; ++ks)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        wA[ks][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (y < HS && 16 * ks + 8 * h + 4 * q < HS) wA[ks][q] = *(const f32x4*)(p + 16 * ks + 4 * q);
+      }
+  };
+  if ((int)blockIdx.x < B) load_rows(blockIdx.x);
+
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const float alpha = ab[b * 3 + 0], beta = ab[b * 3 + 1];
+    const float cpsf = KP / (beta * beta);
+    float mabs = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 7; ++ks)
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) mabs = fmaxf(mabs, fabsf(wA[ks][q][j]));      // (rows / columns outside are 0)
+    for (int i = tid; i < PS; i += 256) { const float t = (float)(i - 49); g[i] = expf(-cpsf * t * t); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mabs = fmaxf(mabs, __shfl_xor(mabs, o));
+    if (lane == 0) red[w] = mabs;
+    __syncthreads();                                                      // (1) g, red
+    mabs = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    build_toeplitz(Tc, g, G_SCALE, tid);
+
+    const float sW = pow2_scale_to_2p13(mabs);
+    const float gbound = fminf(99.0f, 1.0f + sqrtf(3.14159265f / cpsf));   // sum_d g(d) <= 1 + sqrt(pi / c)
+    const float sR = pow2_scale_to_2p13(mabs * gbound);
+    f16x8 a_hi[7], a_lo[7];
+#pragma unroll
+    for (int ks = 0; ks < 7; ++ks)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float t = wA[ks][j >> 2][j & 3] * sW;
+        const _Float16 hi = (_Float16)t;
+        a_hi[ks][j] = hi;
+        a_lo[ks][j] = (_Float16)(t - (float)hi);
+      }
+    __syncthreads();                                                      // (2) table copies
+
+    f32x16 acc[4];
+    zero_acc(acc);
+    gemm_rows_toeplitz(acc, a_hi, a_lo, Tc, laneT);                       // R = W G
+    if (w < 3) store_rt<false>(acc, sR / (sW * G_SCALE), RT, w, h, li);
+    else store_rt<true>(acc, sR / (sW * G_SCALE), RT, w, h, li);
+    __syncthreads();                                                      // (3) R^T
+    zero_acc(acc);
+    gemm_toeplitz_rt(acc, Tc, RT, laneT, w, h, li);                       // G R
+
+    if (b + (int)gridDim.x < B) load_rows(b + gridDim.x);    // the A planes are dead: their registers take the next rows
+
+    // ---- plain store from the accumulators: row yb + (r & 3) + 8 (r >> 2), column 32 nt + li (tile 3: x = 96..99 only).
+    // Lane constants from an opaque copy, as in the forward's epilogue (no hoisted per-row addresses).
+    int li_o = li, h_o = h;
+    asm volatile("" : "+v"(li_o), "+v"(h_o));
+    const float f2 = alpha / (G_SCALE * sR);
+    float* op = dd + (size_t)b * NPIX + li_o;
+    const int yb = 32 * w + 4 * h_o;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int yy = yb + (r & 3) + 8 * (r >> 2);
+      if (yy < HS) {
+        op[yy * HS] = acc[0][r] * f2;
+        op[yy * HS + 32] = acc[1][r] * f2;
+        op[yy * HS + 64] = acc[2][r] * f2;
+        if (li_o < HS - 96) op[yy * HS + 96] = acc[3][r] * f2;
+      }
+    }
+    __syncthreads();                                                      // (4) LDS free for the next sample
+  }
+}
+
 extern "C" int tpsf_forward(const float* depth, const float* alpha_beta, float* HR, float* LR_deg, float* psf,
                             int B, void* stream) {
   if (!depth || !alpha_beta || !HR || !LR_deg || !psf || B <= 0) return TSR_ERR_ARG;
@@ -738,9 +931,41 @@ extern "C" int tpsf_backward(const float* depth, const float* alpha_beta, const 
                              float* d_alpha_beta, float* work, int B, void* stream) {
   if (!depth || !alpha_beta || !HR || !dLR_deg || !d_alpha_beta || !work || B <= 0) return TSR_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(tpsf_bwd_pool_kernel, dim3(B < 2048 ? B : 2048), dim3(256), 0, st, depth, alpha_beta, HR, dLR_deg,
-                     d_alpha_beta, work, B);
+  hipLaunchKernelGGL((tpsf_bwd_pool_kernel<true, false>), dim3(B < 2048 ? B : 2048), dim3(256), 0, st, depth, alpha_beta,
+                     HR, dLR_deg, (const float*)nullptr, d_alpha_beta, work, B);
   const int grid = B < 256 * TPSF_BWD_OCC ? B : 256 * TPSF_BWD_OCC;      // persistent workgroups, TPSF_BWD_OCC per CU
   hipLaunchKernelGGL(tpsf_bwd_dhb_kernel, dim3(grid), dim3(256), 0, st, depth, alpha_beta, work, d_alpha_beta, B);
+  return tsr_check_launch();
+}
+
+extern "C" int tpsf_backward_ex(const float* depth, const float* alpha_beta, const float* HR, const float* dLR_deg,
+                                const float* dHR, const float* dpsf, float* d_alpha_beta, float* d_depth, float* work,
+                                int B, void* stream) {
+  if (!depth || !alpha_beta || !HR || !d_alpha_beta || !work || B <= 0) return TSR_ERR_ARG;
+  if (!dLR_deg && !dHR && !dpsf) return TSR_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 pgrid(B < 2048 ? B : 2048), blk(256);
+  if (dLR_deg || dHR) {
+    if (dLR_deg && dHR)
+      hipLaunchKernelGGL((tpsf_bwd_pool_kernel<true, true>), pgrid, blk, 0, st, depth, alpha_beta, HR, dLR_deg, dHR,
+                         d_alpha_beta, work, B);
+    else if (dLR_deg)
+      hipLaunchKernelGGL((tpsf_bwd_pool_kernel<true, false>), pgrid, blk, 0, st, depth, alpha_beta, HR, dLR_deg, dHR,
+                         d_alpha_beta, work, B);
+    else
+      hipLaunchKernelGGL((tpsf_bwd_pool_kernel<false, true>), pgrid, blk, 0, st, depth, alpha_beta, HR, dLR_deg, dHR,
+                         d_alpha_beta, work, B);
+    const int grid = B < 256 * TPSF_BWD_OCC ? B : 256 * TPSF_BWD_OCC;
+    hipLaunchKernelGGL(tpsf_bwd_dhb_kernel, dim3(grid), blk, 0, st, depth, alpha_beta, work, d_alpha_beta, B);
+    if (dpsf) hipLaunchKernelGGL((tpsf_bwd_psf_kernel<true>), pgrid, blk, 0, st, alpha_beta, dpsf, d_alpha_beta, B);
+    if (d_depth) {
+      const int dgrid = B < 256 * TPSF_FWD_OCC ? B : 256 * TPSF_FWD_OCC;
+      hipLaunchKernelGGL(tpsf_bwd_depth_kernel, dim3(dgrid), blk, 0, st, work, alpha_beta, d_depth, B);
+    }
+  } else {
+    // dpsf alone: no per-pixel dL/dHR, so nothing reaches the depth and `work` is not written
+    hipLaunchKernelGGL((tpsf_bwd_psf_kernel<false>), pgrid, blk, 0, st, alpha_beta, dpsf, d_alpha_beta, B);
+    if (d_depth && hipMemsetAsync(d_depth, 0, (size_t)B * NPIX * sizeof(float), st) != hipSuccess) return TSR_ERR_LAUNCH;
+  }
   return tsr_check_launch();
 }

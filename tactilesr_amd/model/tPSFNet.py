@@ -9,6 +9,17 @@ batch is replaced by one batched HIP launch (the separable PSF convolution as tw
 matrix cores, csrc/tpsf_mfma.hip), the MLP runs on an fp32-MFMA SGEMM, and the
 whole forward is one ``autograd.Function`` so ``Trainer_tPSF.train_cal_loss``'s
 ``MSE(LR[:,2:3], LR_deg).backward()`` (train/tPSFNet_train.py:180-190) reaches the MLP weights.
+
+Autograd covers what the reference's plain-torch forward covers: ``HR``, ``LR_deg`` and ``alphaBeta`` are differentiable,
+``psf`` is once ``net.differentiable_psf = True`` is set (off by default: callers of this drop-in read the returned psf as
+a plain array -- ``psf.cpu().numpy()`` -- which a tensor that requires grad refuses), and both inputs receive gradients
+when they ask for them -- ``depth`` (the inverse problem: fit a contact depth map through the PSF model) and ``x``
+(through the MLP's first layer).  The trainer's own
+loss -- gradients arriving through ``LR_deg`` / ``alphaBeta`` only, no input gradient wanted -- still runs
+``tpsf_backward``, launch for launch; anything else runs ``tpsf_backward_ex`` (include/tactilesr_hip.h has the formulas).
+As in the reference, two things are NOT differentiated: the plateau threshold ``depth.max() - 1e-3`` and the plateau's
+fill value (a detached constant), so a loss on ``HR`` sees no gradient from the plateau pixels of the output, while the
+depth pixels under the plateau still receive theirs.
 No CPU fallback.
 """
 from __future__ import annotations
@@ -88,12 +99,15 @@ class _TPSFFn(torch.autograd.Function):
         psf = torch.empty(B, 1, 99, 99, dtype=torch.float32, device=x.device)
         call("tpsf_forward", ptr(d), ptr(ab), ptr(HR), ptr(LRd), ptr(psf), _I(B), stream())
         ctx.h, ctx.d, ctx.params, ctx.owner = h, d, params, owner
+        ctx.x_meta, ctx.depth_meta = (x.shape, x.dtype), (depth.shape, depth.dtype)
         ctx.token = _Token()
         if any(ctx.needs_input_grad):
             from ..ddp import note_forward
             note_forward(owner, ctx.token)     # the flat gradient buffer goes only to the sole pending backward
         ctx.save_for_backward(HR)          # the backward's reductions read the stored output: an in-place edit of the
-        ctx.mark_non_differentiable(HR, psf)      # returned HR before backward() trips autograd's version check
+        #                                    returned HR before backward() trips autograd's version check
+        if not getattr(owner, "differentiable_psf", False):
+            ctx.mark_non_differentiable(psf)
         ctx.set_materialize_grads(False)   # no zero-filled (B,1,100,100) / (B,1,99,99) gradients for the unused outputs
         return HR, LRd, psf, ab.view(B, 1, 3).clone()
 
@@ -104,12 +118,29 @@ class _TPSFFn(torch.autograd.Function):
         B = h[0].shape[0]
         dev = d.device
         dab = torch.empty(B, 3, dtype=torch.float32, device=dev)
-        if gLR is not None:
-            work = torch.empty(B * 10000, dtype=torch.float32, device=dev)
-            call("tpsf_backward", ptr(d), ptr(h[-1]), ptr(ctx.saved_tensors[0]), ptr(gLR.contiguous().float()), ptr(dab),
-                 ptr(work), _I(B), stream())
+        need_x, need_depth = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        d_depth = None
+        if gHR is None and gpsf is None and not need_depth:
+            # the trainer's loss (gradients through LR_deg / alphaBeta only): tpsf_backward, as ever
+            if gLR is not None:
+                work = torch.empty(B * 10000, dtype=torch.float32, device=dev)
+                call("tpsf_backward", ptr(d), ptr(h[-1]), ptr(ctx.saved_tensors[0]), ptr(gLR.contiguous().float()), ptr(dab),
+                     ptr(work), _I(B), stream())
+            else:
+                dab.zero_()
+        elif gHR is None and gLR is None and gpsf is None:
+            dab.zero_()                    # only alphaBeta carries a gradient: none of it reaches the depth
+            d_depth = torch.zeros(B, 100, 100, dtype=torch.float32, device=dev)
         else:
-            dab.zero_()
+            up = [None if t is None else t.contiguous().float() for t in (gLR, gHR, gpsf)]
+            work = torch.empty(B * 10000, dtype=torch.float32, device=dev)
+            if need_depth:
+                d_depth = torch.empty(B, 100, 100, dtype=torch.float32, device=dev)
+            call("tpsf_backward_ex", ptr(d), ptr(h[-1]), ptr(ctx.saved_tensors[0]), ptr(up[0]), ptr(up[1]), ptr(up[2]),
+                 ptr(dab), ptr(d_depth), ptr(work), _I(B), stream())
+        if d_depth is not None:
+            shape, dtype = ctx.depth_meta
+            d_depth = d_depth.view(shape).to(dtype)
         if gab is not None:
             dab = dab + gab.reshape(B, 3)
         # gradient plan: the flat buffer is handed to autograd only when no .grad exists yet (zero_grad()'s default) and
@@ -146,7 +177,17 @@ class _TPSFFn(torch.autograd.Function):
                      _I(N), stream())
                 dy = dx
         call("tsr_reduce_splits", ptr(slab), ptr(out), _L(tot), _I(ns), _lib.c_float(1.0), stream())
-        return (None, None, None) + tuple(plan.view(i, out) for i in range(8))
+        dx = None
+        if need_x:
+            # the first layer has no ReLU below it: dx = dy W0, in the shape x came in
+            w = ws[0].detach().contiguous()
+            N, K = w.shape
+            dx = torch.empty(B, K, dtype=torch.float32, device=dev)
+            call("tsr_sgemm", ptr(dy), _L(N), _L(1), ptr(w), _L(K), _L(1), ptr(None), ptr(dx), _I(B), _I(K), _I(N), _I(0),
+                 stream())
+            shape, dtype = ctx.x_meta
+            dx = dx.view(shape).to(dtype)
+        return (None, dx, d_depth) + tuple(plan.view(i, out) for i in range(8))
 
 
 class tPSFNet(nn.Module):
@@ -173,6 +214,7 @@ class tPSFNet(nn.Module):
             for b in range(4):
                 m[a, b] = ((xs.view(-1, 1) - (12 + 25 * a)) ** 2 + (xs.view(1, -1) - (12 + 25 * b)) ** 2) ** 0.5
         self.LR_masking_sdf = 10 * (m - m.min()) / (m.max() - m.min())
+        self.differentiable_psf = False   # True: the returned psf carries gradients too (see the module docstring)
         self._grad_plan = None            # flat gradient buffer + split-K slab (created by the first backward)
         self._shared_graph = False
         assert abs(float(sdf.max()) - math.sqrt(4802.0)) < 1e-3 and abs(float(m.max()) - math.sqrt(15138.0)) < 1e-3
