@@ -20,7 +20,8 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr, stream
-from .tactileSR_model import NS_F32, NS_F16X3, NS_B16, NS_B16K, NS_B16K_PAIR, _SlotPool, _timed, to_cb16, from_cb16
+from .tactileSR_model import (NS_F32, NS_F16X3, NS_B16, NS_B16K, NS_B16K_PAIR, _SlotPool, _timed, _twin_args, _pack_form,
+                              _pack_pair_b16k, to_cb16, from_cb16)
 
 _I, _F, _D, _L = c_int, c_float, c_double, c_longlong
 
@@ -244,46 +245,23 @@ def conv_ex(*, B, H, W, src: Act, w, cout, ks, out, out_ctot, out_coff, scale=No
         raise _lib.TactileSRHipError(f"tsr_conv2d_ex failed: status {st}")
 
 
-def _pack(w, cout, cin, ks, nsplit=0, w_amax=None):
-    if nsplit == NS_B16:      # bf16 activation storage: the weights are the one-plane bf16 pack
-        nsplit = 1
-    if nsplit == NS_F16X3:
-        n = _lib.load().tsr_conv_weight_bf16s_elems(cout, cin, ks, 2)
-        wp = torch.empty(n, dtype=torch.float16, device=w.device)
-        call("tsr_pack_conv_weight_f16s_dev", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), ptr(w_amax), stream())
-        return wp
-    if nsplit:
-        n = _lib.load().tsr_conv_weight_bf16s_elems(cout, cin, ks, nsplit)
-        wp = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-        call("tsr_pack_conv_weight_bf16s", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), _I(nsplit), stream())
-        return wp
-    wp = torch.empty(cout * cin * ks * ks, dtype=torch.float32, device=w.device)
-    call("tsr_pack_conv_weight", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), stream())
+def _pack_dev(w, ints, nsplit, w_amax):
+    """Pack `w` for a train launch of arithmetic `nsplit` (fp16 planes: scaled from the device scalar `w_amax`); `ints`:
+    (cout, cin, ks) for the forward conv, (cout, cin, ks, ci0, nprime) for d(input)[ci0:ci0+nprime]."""
+    dgrad = len(ints) == 5
+    out, cin = (ints[4], ints[0]) if dgrad else ints[:2]
+    name, n, dtype, tail = _pack_form(nsplit, out, cin, ints[2], dgrad=dgrad, dev_amax=True)
+    wp = torch.empty(n, dtype=dtype, device=w.device)
+    call(name, ptr(w), ptr(wp), *map(_I, ints), *((ptr(w_amax),) if nsplit == NS_F16X3 else tail), stream())
     return wp
+
+
+def _pack(w, cout, cin, ks, nsplit=0, w_amax=None):
+    return _pack_dev(w, (cout, cin, ks), nsplit, w_amax)
 
 
 def _pack_dgrad(w, cout, cin, ks, ci0, nprime, nsplit=0, w_amax=None):
-    if nsplit == NS_B16K:     # bf16 activation storage, the launch runs csrc/conv_b16k.hip: that kernel's slab layout
-        wp = torch.empty(_lib.load().tsr_conv_weight_b16k_elems(nprime, cout, ks), dtype=torch.bfloat16, device=w.device)
-        call("tsr_pack_conv_weight_dgrad_b16k", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), _I(ci0), _I(nprime), stream())
-        return wp
-    if nsplit == NS_B16:
-        nsplit = 1
-    if nsplit == NS_F16X3:
-        n = _lib.load().tsr_conv_weight_bf16s_elems(nprime, cout, ks, 2)
-        wp = torch.empty(n, dtype=torch.float16, device=w.device)
-        call("tsr_pack_conv_weight_dgrad_f16s_dev", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), _I(ci0), _I(nprime),
-             ptr(w_amax), stream())
-        return wp
-    if nsplit:
-        n = _lib.load().tsr_conv_weight_bf16s_elems(nprime, cout, ks, nsplit)
-        wp = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-        call("tsr_pack_conv_weight_dgrad_bf16s", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), _I(ci0), _I(nprime),
-             _I(nsplit), stream())
-        return wp
-    wp = torch.empty(nprime * cout * ks * ks, dtype=torch.float32, device=w.device)
-    call("tsr_pack_conv_weight_dgrad", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), _I(ci0), _I(nprime), stream())
-    return wp
+    return _pack_dev(w, (cout, cin, ks, ci0, nprime), nsplit, w_amax)
 
 
 TRAIN_IMPLS = {"f32": NS_F32, "bf16x6": 3, "fp16x3": NS_F16X3, "bf16": NS_B16, "bf16op": 1}
@@ -381,24 +359,18 @@ class TrainEngine:
             torch._foreach_add_(c.nbt, 1)
             c.nbt = []
 
+    def _twin(self, name, *args, amax=()):
+        """A glue launch in the engine's storage type: `name + "_b16"` under bf16 storage, else `name` with its `amax` pointer."""
+        call(*_twin_args(self.io16, name, args, amax), stream())
+
     def _stem(self, x, ctot_in, coff, A, hin, win, sf, w, dst, relu, B, am):
         """bilinear x sf + conv 3 -> 64 (raw or ReLU'd) into a 64-channel CB16 buffer of the engine's storage type."""
-        if self.io16:
-            call("tsr_stem_fwd_b16", ptr(x), _I(ctot_in), _I(coff), _I(A), _I(hin), _I(win), _I(sf), ptr(w), ptr(None),
-                 ptr(None), ptr(dst), _I(64), _I(0), _I(relu), _I(B), stream())
-        else:
-            call("tsr_stem_fwd", ptr(x), _I(ctot_in), _I(coff), _I(A), _I(hin), _I(win), _I(sf), ptr(w), ptr(None),
-                 ptr(None), ptr(dst), _I(64), _I(0), _I(relu), _I(B), ptr(am), stream())
+        self._twin("tsr_stem_fwd", ptr(x), _I(ctot_in), _I(coff), _I(A), _I(hin), _I(win), _I(sf), ptr(w), ptr(None),
+                   ptr(None), ptr(dst), _I(64), _I(0), _I(relu), _I(B), amax=(am,))
 
-    def _entries(self, c, cout, ks, nsplit=None):
-        """Statistics-slab entries the conv launch (cout, ks) of this engine's arithmetic (or of the form `nsplit`) writes."""
-        return _lib.load().tsr_conv2d_slab_entries_ex(c.B, c.H, c.W, cout, ks, self.nsplit if nsplit is None else nsplit)
-
-    def _packw(self, c, conv):
-        """(packed weight, device scalar max|w| or None)"""
-        w = conv.weight.detach().contiguous()
-        wa = c.wamax.get(id(conv))
-        return _pack(w, w.shape[0], w.shape[1], w.shape[2], self.nsplit, wa), wa
+    def _entries(self, c, cout, ks, nsplit):
+        """Statistics-slab entries the conv launch (cout, ks) of the form `nsplit` writes."""
+        return _lib.load().tsr_conv2d_slab_entries_ex(c.B, c.H, c.W, cout, ks, nsplit)
 
     def _plain(self, c, a: Act) -> Act:
         """bf16 storage: `a` as a tensor the LDS-DMA kernels (conv_b16k / wgrad_b16k: operands go from HBM to LDS as stored)
@@ -416,12 +388,30 @@ class TrainEngine:
         """bf16 storage: this forward conv shape runs csrc/conv_b16k.hip (tsr_conv2d_ex, NS_B16K)."""
         return self.io16 and ks > 1 and bool(_lib.load().tsr_conv2d_ex_dgrad_b16k(cout, cin, ks))
 
-    def _packw_b16k(self, conv):
+    def _form(self, c, conv, src: Act, dgrad=None):
+        """What a training conv launches: (source, packed weight, device scalar max|w| or None, `nsplit` code of the launch).
+        `dgrad` None: the forward conv of `conv` on `src`.  Under bf16 storage, the 3x3 / 5x5 shapes csrc/conv_b16k.hip has
+        run there (NS_B16K) on a plain source -- a virtual one is materialised -- and the 1x1 shapes csrc/conv1x1_b16k.hip
+        has run there on the source as it is: that kernel transforms a virtual input in LDS behind the DMA.
+        `dgrad` = (ci0, nprime, plain): d(input)[ci0:ci0+nprime] given dz = `src`; under bf16 storage conv_b16k runs it
+        (same tensors, its own pack) when the launch's tensors are `plain` and the kernel has the flipped shape.
+        Everything else runs the engine's arithmetic."""
         w = conv.weight.detach().contiguous()
         cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
-        wp = torch.empty(_lib.load().tsr_conv_weight_b16k_elems(cout, cin, ks), dtype=torch.bfloat16, device=w.device)
-        call("tsr_pack_conv_weight_b16k", ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), stream())
-        return wp
+        wa = c.wamax.get(id(conv))
+        ints = (cout, cin, ks)
+        if dgrad is not None:
+            ci0, nprime, plain = dgrad
+            ints += (ci0, nprime)
+            b16k = self.io16 and plain and _lib.load().tsr_conv2d_ex_dgrad_b16k(nprime, cout, ks)
+        elif ks > 1:
+            b16k = self._b16k(cout, cin, ks)
+            if b16k:
+                src = self._plain(c, src)
+        else:
+            b16k = self.io16 and _lib.load().tsr_conv2d_ex_fwd1x1_b16k(cout, cin)
+        ns = NS_B16K if b16k else self.nsplit
+        return src, _pack_dev(w, ints, ns, wa), wa, ns
 
     def _pair_bn(self, c: _Ctx, X: Act, blk, cat1):
         """bf16 storage: conv_3_1 || conv_5_1 of an MSRB (reference model/tactileSR_model.py:198-200) as ONE 5x5 launch with
@@ -431,15 +421,13 @@ class TrainEngine:
         if b3.momentum != b5.momentum or b3.eps != b5.eps or (c3.bias is None) != (c5.bias is None):
             raise _lib.TactileSRHipError("stage-1 pair: the two conv + BatchNorm layers differ in momentum / eps / bias")
         cin = c3.weight.shape[1]
-        w = torch.cat([torch.nn.functional.pad(c3.weight.detach(), (1, 1, 1, 1)), c5.weight.detach()], 0).contiguous()
-        wp = torch.empty(_lib.load().tsr_conv_weight_b16k_pair_elems(cin), dtype=torch.bfloat16, device=w.device)
-        call("tsr_pack_conv_weight_b16k_pair", ptr(w), ptr(wp), _I(cin), stream())
+        wp = _pack_pair_b16k(c3.weight.detach(), c5.weight.detach())
         with _timed(self.profile, ("fwd", 5, 128, cin)):
             # (the pair form only knows epi_mode 1: with both layers in eval mode its statistics slab is simply not read)
             conv_ex(B=c.B, H=c.H, W=c.W, src=self._plain(c, X), w=wp, cout=128, ks=5, out=cat1, out_ctot=128, out_coff=0,
                     epi_mode=1, slab=c.slab, slab_cnt=c.slab_cnt, nsplit=NS_B16K_PAIR)
         cat = lambda a, b: torch.cat([a.detach(), b.detach()])
-        vec = torch.empty(4, 128, dtype=torch.float32, device=w.device)
+        vec = torch.empty(4, 128, dtype=torch.float32, device=wp.device)
         rm, rv = cat(b3.running_mean, b5.running_mean), cat(b3.running_var, b5.running_var)
         bias = cat(c3.bias, c5.bias) if c3.bias is not None else None
         gamma, beta = cat(b3.weight, b5.weight), cat(b3.bias, b5.bias)     # (named: a temporary's block would be reused)
@@ -448,8 +436,8 @@ class TrainEngine:
             ev = self._bn_eval_vectors(bias, gamma, beta, rm, rv, b3.eps, 128)      # (before the finalize below moves rm / rv)
             if all(held):
                 return ev
-        call("tsr_bn_stats_finalize", ptr(c.slab), ptr(c.slab_cnt), _I(self._entries(c, 128, 5)), _I(128), ptr(bias),
-             ptr(gamma), ptr(beta), ptr(rm), ptr(rv), _F(b3.momentum), _F(b3.eps),
+        call("tsr_bn_stats_finalize", ptr(c.slab), ptr(c.slab_cnt), _I(self._entries(c, 128, 5, NS_B16K_PAIR)), _I(128),
+             ptr(bias), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), _F(b3.momentum), _F(b3.eps),
              ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), ptr(vec[3]), ptr(c.work), stream())
         for h, bnm, sl in ((held[0], b3, slice(0, 64)), (held[1], b5, slice(64, 128))):
             if h:          # a mixed pair: this half keeps its statistics and takes the running-statistics vectors
@@ -464,10 +452,7 @@ class TrainEngine:
         """conv (bias-free raw output) + batch statistics; returns the 4xC BN vectors."""
         w = conv.weight
         cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
-        if self._b16k(cout, cin, ks):
-            src, wp, wis, ns = self._plain(c, src), self._packw_b16k(conv), None, NS_B16K
-        else:
-            (wp, wis), ns = self._packw(c, conv), self.nsplit
+        src, wp, wis, ns = self._form(c, conv, src)
         if not bn.training:      # eval-mode BatchNorm: the raw output alone (epi_mode 0, no scale / shift / ReLU), no statistics
             with _timed(self.profile, ("fwd", ks, cout, cin)):
                 conv_ex(B=c.B, H=c.H, W=c.W, src=src, w=wp, cout=cout, ks=ks, out=out, out_ctot=out_ctot,
@@ -477,7 +462,7 @@ class TrainEngine:
             conv_ex(B=c.B, H=c.H, W=c.W, src=src, w=wp, cout=cout, ks=ks, out=out, out_ctot=out_ctot,
                     out_coff=out_coff, epi_mode=1, slab=c.slab, slab_cnt=c.slab_cnt, nsplit=ns,
                     w_amax=wis, out_amax=out_amax)
-        return self._bn_finalize(c, conv.bias, bn, c.slab, c.slab_cnt, self._entries(c, cout, ks), cout)
+        return self._bn_finalize(c, conv.bias, bn, c.slab, c.slab_cnt, self._entries(c, cout, ks, ns), cout)
 
     # ------------------------------------------------------------------ forward
     def _new_ctx(self, B, H, W, dev):
@@ -524,13 +509,9 @@ class TrainEngine:
         s.bn_c2[:, 128:256] = self._conv_bn(c, A1, blk.conv_5_2[0], blk.conv_5_2[1], s.cat2, 256, 128, am_c2)
         A2 = Act(s.cat2, 256, 0, 256, s.bn_c2[0], s.bn_c2[1], s.bn_c2[2], s.bn_c2[3], amax=am_c2)
         s.A1, s.A2 = A1, A2
-        if self.io16 and _lib.load().tsr_conv2d_ex_fwd1x1_b16k(64, 256):
-            # bf16 storage: the virtual 256-channel input is transformed in LDS behind the DMA (csrc/conv1x1_b16k.hip)
-            wp, wis, nsc = self._packw_b16k(blk.confusion), None, NS_B16K
-        else:
-            (wp, wis), nsc = self._packw(c, blk.confusion), self.nsplit
+        src, wp, wis, nsc = self._form(c, blk.confusion, A2)
         with _timed(self.profile, ("fwd", 1, 64, 256)):
-            conv_ex(B=c.B, H=c.H, W=c.W, src=A2, w=wp, cout=64, ks=1, out=out, out_ctot=octot, out_coff=ocoff,
+            conv_ex(B=c.B, H=c.H, W=c.W, src=src, w=wp, cout=64, ks=1, out=out, out_ctot=octot, out_coff=ocoff,
                     shift=blk.confusion.bias.detach(), relu=1, res=X, nsplit=nsc, w_amax=wis,
                     out_amax=am_o)
         s.Y = Act(out, octot, ocoff, 64, amax=am_o)
@@ -542,17 +523,13 @@ class TrainEngine:
         s.X = F0
         s.f1 = buf(64)
         s.F1 = Act(s.f1, 64, 0, 64, amax=new_amax())
-        if self._b16k(64, 64, 3) and F0.scale is None:       # bf16 storage: both convs on conv_b16k's plain mode
-            (w1, wis1), (w2, wis2), nsr = (self._packw_b16k(rb.conv1), None), (self._packw_b16k(rb.conv2), None), NS_B16K
-        else:
-            w1, wis1 = self._packw(c, rb.conv1)
-            w2, wis2 = self._packw(c, rb.conv2)
-            nsr = self.nsplit
+        src1, w1, wis1, ns1 = self._form(c, rb.conv1, F0)
+        src2, w2, wis2, ns2 = self._form(c, rb.conv2, s.F1)
         with _timed(self.profile, ("fwd", 3, 64, 64)):
-            conv_ex(B=c.B, H=c.H, W=c.W, src=F0, w=w1, cout=64, ks=3, out=s.f1, out_ctot=64, out_coff=0,
-                    shift=rb.conv1.bias.detach(), relu=1, nsplit=nsr, w_amax=wis1, out_amax=s.F1.amax)
-            conv_ex(B=c.B, H=c.H, W=c.W, src=s.F1, w=w2, cout=64, ks=3, out=out, out_ctot=octot,
-                    out_coff=ocoff, shift=rb.conv2.bias.detach(), relu=1, res=F0, nsplit=nsr,
+            conv_ex(B=c.B, H=c.H, W=c.W, src=src1, w=w1, cout=64, ks=3, out=s.f1, out_ctot=64, out_coff=0,
+                    shift=rb.conv1.bias.detach(), relu=1, nsplit=ns1, w_amax=wis1, out_amax=s.F1.amax)
+            conv_ex(B=c.B, H=c.H, W=c.W, src=src2, w=w2, cout=64, ks=3, out=out, out_ctot=octot,
+                    out_coff=ocoff, shift=rb.conv2.bias.detach(), relu=1, res=F0, nsplit=ns2,
                     w_amax=wis2, out_amax=am_o)
         s.Y = Act(out, octot, ocoff, 64, amax=am_o)
         return s
@@ -568,8 +545,8 @@ class TrainEngine:
         check_trainable_size(H, W)          # before any launch: a refused step leaves parameters and statistics as they were
         c = self._new_ctx(B, H, W, dev)
         c.x, c.hin, c.win = x.detach(), hin, win
-        c.want_dx = False        # TactileSRTrainFn sets it when the taxels require grad: backward then also returns dx
-        c.want = self._want_default(m.named_parameters())      # (TactileSRTrainFn: what autograd asks for instead)
+        c.want_dx = False        # TrainFn sets it when the taxels require grad: backward then also leaves c.dx
+        c.want = self._want_default(m.named_parameters())      # (TrainFn: what autograd asks for instead)
         st_entries = c.st_entries
 
         def buf(ch):
@@ -588,8 +565,7 @@ class TrainEngine:
             am = new_amax()
             self._stem(x, ctot_in, A * t, A, hin, win, sf, seq[1].weight.detach(), z1, 0, B, am)
             if seq[2].training:
-                call("tsr_cb16_stats_b16" if self.io16 else "tsr_cb16_stats", ptr(z1), _I(64), _I(0), _I(B), _I(HW),
-                     ptr(c.slab), ptr(c.slab_cnt), stream())
+                self._twin("tsr_cb16_stats", ptr(z1), _I(64), _I(0), _I(B), _I(HW), ptr(c.slab), ptr(c.slab_cnt))
                 v1 = self._bn_finalize(c, None, seq[2], c.slab, c.slab_cnt, st_entries, 64)
             else:
                 v1 = self._bn_held_vec(None, seq[2], 64)
@@ -639,15 +615,12 @@ class TrainEngine:
             c.res.append(s)
         # ---- head
         c.h0 = buf(128)
-        if self._b16k(128, 128, 3):
-            wh, wish, nsh = self._packw_b16k(m.output_layer[0]), None, NS_B16K
-        else:
-            (wh, wish), nsh = self._packw(c, m.output_layer[0]), self.nsplit
-        conv_ex(B=B, H=H, W=W, src=Act(c.hcat, 128, 0, 128, amax=c.am_hcat), w=wh, cout=128, ks=3, out=c.h0,
-                out_ctot=128, out_coff=0, relu=1, nsplit=nsh, w_amax=wish)
+        HC, wh, wish, nsh = self._form(c, m.output_layer[0], Act(c.hcat, 128, 0, 128, amax=c.am_hcat))
+        conv_ex(B=B, H=H, W=W, src=HC, w=wh, cout=128, ks=3, out=c.h0, out_ctot=128, out_coff=0, relu=1, nsplit=nsh,
+                w_amax=wish)
         out = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
-        call("tsr_head_fwd_b16" if self.io16 else "tsr_head_fwd", ptr(c.h0), _I(128), _I(128),
-             ptr(m.output_layer[2].weight.detach()), ptr(out), _I(1), _I(B), _I(H), _I(W), stream())
+        self._twin("tsr_head_fwd", ptr(c.h0), _I(128), _I(128), ptr(m.output_layer[2].weight.detach()), ptr(out), _I(1),
+                   _I(B), _I(H), _I(W))
         c.out = out
         self._bump_nbt(c)
         self.last_ctx = c if self.keep_ctx else None
@@ -742,26 +715,21 @@ class TrainEngine:
 
     def _dgrad(self, c, dz: Act, conv, ci0, nprime, out, out_ctot, out_coff, res: Act = None, mask: Act = None,
                bn=False, out_amax=None):
-        """d(input)[ci0:ci0+nprime] of conv given dz; optional + res, ReLU mask, BN-backward sums."""
-        w = conv.weight.detach().contiguous()
-        cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
-        wa = c.wamax.get(id(conv))
-        # bf16 storage: the 128-channel 3x3 / 5x5 dgrads (masked or not) run conv_b16k (NS_B16K; same tensors, its own pack)
-        ns = self.nsplit
-        if self.io16 and dz.scale is None and (res is None or res.scale is None) and \
-                (ks > 1 or (mask is not None and res is None)) and _lib.load().tsr_conv2d_ex_dgrad_b16k(nprime, cout, ks):
-            ns = NS_B16K
-        wp = _pack_dgrad(w, cout, cin, ks, ci0, nprime, ns, wa)
+        """d(input)[ci0:ci0+nprime] of conv given dz; optional + res, ReLU mask, BN-backward sums.  Returns the statistics-slab
+        entries of the launch: what a following `_bn_bwd` reduces."""
+        cout, ks = conv.weight.shape[0], conv.weight.shape[2]
+        # bf16 storage: the 128-channel 3x3 / 5x5 dgrads (masked or not) run conv_b16k
+        plain = dz.scale is None and (res is None or res.scale is None) and (ks > 1 or (mask is not None and res is None))
+        dz, wp, wa, ns = self._form(c, conv, dz, dgrad=(ci0, nprime, plain))
         with _timed(self.profile, ("dgrad", ks, nprime, cout)):
             conv_ex(B=c.B, H=c.H, W=c.W, src=dz, w=wp, cout=nprime, ks=ks, out=out, out_ctot=out_ctot,
                     out_coff=out_coff, res=res, epi_mode=2 if mask is not None else 0, mask=mask, bn=bn,
                     slab=c.slab if bn else None, slab_cnt=None, nsplit=ns, w_amax=wa,
                     out_amax=out_amax)
-        c.last_entries = self._entries(c, nprime, ks, ns)      # what a following _bn_bwd reduces
+        return self._entries(c, nprime, ks, ns)
 
-    def _bn_bwd(self, c, layer, g_buf, g_ctot, g_coff, z: Act, zoff, C, bn_vec, bn_mod, grads, name, out_amax=None,
-                gnames=None):
-        """Finish BatchNorm backward for C channels whose masked gradient g sits in g_buf (slab sums
+    def _bn_bwd(self, c, layer, g_buf, g_ctot, g_coff, z: Act, zoff, C, bn_vec, grads, entries, out_amax=None, gnames=None):
+        """Finish BatchNorm backward for C channels whose masked gradient g sits in g_buf (slab sums, `entries` of them,
         were just produced by the dgrad epilogue over the same C channels).  `gnames` = (weight, bias) parameter names:
         the wanted ones of dgamma / dbeta are then written straight into their gradient slots (no copy launches).
         Plan records ("bn_bwd_finalize", layer) -- needed for dgamma / dbeta or for the apply pass -- and
@@ -779,10 +747,9 @@ class TrainEngine:
         db = grads.dest(gnames[1], (C,)) if gnames[1] else out[1]
         if held:
             if finalize:
-                call("tsr_bn_bwd_finalize_eval", ptr(c.slab), _I(c.last_entries), _I(C), ptr(dg), ptr(db), ptr(c.work),
-                     stream())
+                call("tsr_bn_bwd_finalize_eval", ptr(c.slab), _I(entries), _I(C), ptr(dg), ptr(db), ptr(c.work), stream())
         else:
-            call("tsr_bn_bwd_finalize", ptr(c.slab), _I(c.last_entries), _I(C), _D(float(c.B * c.HW)),
+            call("tsr_bn_bwd_finalize", ptr(c.slab), _I(entries), _I(C), _D(float(c.B * c.HW)),
                  ptr(bn_vec[0]), ptr(bn_vec[2]), ptr(bn_vec[3]), ptr(dg), ptr(db), ptr(out[2]), ptr(out[3]),
                  ptr(out[4]), ptr(c.work), stream())
             # layers that share this launch, one of them in eval mode (a mixed stage-1 pair): dgamma / dbeta are the same sums
@@ -798,19 +765,11 @@ class TrainEngine:
         if ("bn_bwd_apply", layer) not in c.live:
             return out if finalize else None
         if held:
-            if self.io16:
-                call("tsr_bn_bwd_apply_eval_b16", ptr(g_buf), _I(g_ctot), _I(g_coff), ptr(bn_vec[0]), _I(C), _I(c.B),
-                     _I(c.HW), stream())
-            else:
-                call("tsr_bn_bwd_apply_eval", ptr(g_buf), _I(g_ctot), _I(g_coff), ptr(bn_vec[0]), _I(C), _I(c.B), _I(c.HW),
-                     ptr(out_amax), stream())
+            self._twin("tsr_bn_bwd_apply_eval", ptr(g_buf), _I(g_ctot), _I(g_coff), ptr(bn_vec[0]), _I(C), _I(c.B), _I(c.HW),
+                       amax=(out_amax,))
             return out if finalize else None
-        if self.io16:
-            call("tsr_bn_bwd_apply_b16", ptr(g_buf), _I(g_ctot), _I(g_coff), ptr(z.buf), _I(z.ctot), _I(z.coff + zoff),
-                 ptr(out[2]), ptr(out[3]), ptr(out[4]), _I(C), _I(c.B), _I(c.HW), stream())
-        else:
-            call("tsr_bn_bwd_apply", ptr(g_buf), _I(g_ctot), _I(g_coff), ptr(z.buf), _I(z.ctot), _I(z.coff + zoff),
-                 ptr(out[2]), ptr(out[3]), ptr(out[4]), _I(C), _I(c.B), _I(c.HW), ptr(out_amax), stream())
+        self._twin("tsr_bn_bwd_apply", ptr(g_buf), _I(g_ctot), _I(g_coff), ptr(z.buf), _I(z.ctot), _I(z.coff + zoff),
+                   ptr(out[2]), ptr(out[3]), ptr(out[4]), _I(C), _I(c.B), _I(c.HW), amax=(out_amax,))
         return out   # rows 0,1 = dgamma, dbeta
 
     def _res_bwd(self, c, s, rb, name, dpre: Act, grads, new_amax, buf, mask_input=True):
@@ -838,41 +797,40 @@ class TrainEngine:
         """Backward of one MSRB.  `dpre` = gradient w.r.t. the block output BEFORE its ReLU; returns the gradient w.r.t.
         the block input (None when the backward plan has no launch producing it): masked by the input's ReLU pattern / with
         the BatchNorm-backward sums of a virtual input (`mask_input`, the chained engine; `in_bn`: that BatchNorm's path) or
-        plain (standalone module)."""
+        plain (standalone module) -- and the statistics-slab entries of those sums, for the `_bn_bwd` of `in_bn`."""
         name = name + "." if name else ""          # (standalone module: parameter names carry no prefix)
         on = lambda kind, layer: (kind, name + layer) in c.live
         sums = lambda layer: on("bn_bwd_finalize", layer)      # whether the dgrad in front of this BatchNorm leaves its sums
         # confusion 1x1: a = relu(bn(cat2)), dz = dpre
         self._wgrad(c, s.A2, dpre, blk.confusion, grads, name + "confusion", True)
         if not (on("dgrad", "confusion[0:128]") or on("dgrad", "confusion[128:256]")):
-            return None
+            return None, None
         g2 = buf(256)
         am_g2 = [new_amax(), new_amax()]
-        for half, (cv, bnm, nm) in enumerate(((blk.conv_3_2[0], blk.conv_3_2[1], "conv_3_2"),
-                                              (blk.conv_5_2[0], blk.conv_5_2[1], "conv_5_2"))):
+        for half, nm in enumerate(("conv_3_2", "conv_5_2")):
             o = 128 * half
             if not on("dgrad", f"confusion[{o}:{o + 128}]"):
                 continue
             mk = Act(s.cat2, 256, o, 128, s.bn_c2[0, o:o + 128], s.bn_c2[1, o:o + 128], s.bn_c2[2, o:o + 128],
                      s.bn_c2[3, o:o + 128])
-            self._dgrad(c, dpre, blk.confusion, o, 128, g2, 256, o, mask=mk, bn=sums(nm + ".1"))
-            self._bn_bwd(c, f"{name}{nm}.1", g2, 256, o, Act(s.cat2, 256, 0, 256), o, 128, s.bn_c2[:, o:o + 128], bnm, grads,
-                         nm, out_amax=am_g2[half], gnames=(f"{name}{nm}.1.weight", f"{name}{nm}.1.bias"))
+            e = self._dgrad(c, dpre, blk.confusion, o, 128, g2, 256, o, mask=mk, bn=sums(nm + ".1"))
+            self._bn_bwd(c, f"{name}{nm}.1", g2, 256, o, Act(s.cat2, 256, 0, 256), o, 128, s.bn_c2[:, o:o + 128], grads, e,
+                         out_amax=am_g2[half], gnames=(f"{name}{nm}.1.weight", f"{name}{nm}.1.bias"))
         if self.debug is not None:
             self.debug[f"{tag}.dz2"] = g2.clone()
         DZ32, DZ52 = Act(g2, 256, 0, 128, amax=am_g2[0]), Act(g2, 256, 128, 128, amax=am_g2[1])
         self._wgrad(c, s.A1, DZ32, blk.conv_3_2[0], grads, f"{name}conv_3_2.0", True)
         self._wgrad(c, s.A1, DZ52, blk.conv_5_2[0], grads, f"{name}conv_5_2.0", True)
         if not on("dgrad", "conv_5_2.0"):          # (the two stage-2 dgrads fill one tensor: both are planned or neither)
-            return None
+            return None, None
         g1 = buf(128)
         self._dgrad(c, DZ32, blk.conv_3_2[0], 0, 128, g1, 128, 0)
         mk = Act(s.cat1, 128, 0, 128, s.bn_c1[0], s.bn_c1[1], s.bn_c1[2], s.bn_c1[3])
-        self._dgrad(c, DZ52, blk.conv_5_2[0], 0, 128, g1, 128, 0, res=Act(g1, 128, 0, 128), mask=mk,
-                    bn=sums("conv_3_1.1|conv_5_1.1"))
+        e = self._dgrad(c, DZ52, blk.conv_5_2[0], 0, 128, g1, 128, 0, res=Act(g1, 128, 0, 128), mask=mk,
+                        bn=sums("conv_3_1.1|conv_5_1.1"))
         am_g1 = new_amax()
-        r = self._bn_bwd(c, f"{name}conv_3_1.1|conv_5_1.1", g1, 128, 0, Act(s.cat1, 128, 0, 128), 0, 128, s.bn_c1, None,
-                         grads, "", out_amax=am_g1)
+        r = self._bn_bwd(c, f"{name}conv_3_1.1|conv_5_1.1", g1, 128, 0, Act(s.cat1, 128, 0, 128), 0, 128, s.bn_c1, grads, e,
+                         out_amax=am_g1)
         for gname, row, lo in ((f"{name}conv_3_1.1.weight", 0, 0), (f"{name}conv_3_1.1.bias", 1, 0),
                                (f"{name}conv_5_1.1.weight", 0, 64), (f"{name}conv_5_1.1.bias", 1, 64)):
             if gname in c.want:
@@ -884,15 +842,15 @@ class TrainEngine:
         self._wgrad(c, s.X, DZ31, blk.conv_3_1[0], grads, f"{name}conv_3_1.0", True)
         self._wgrad(c, s.X, DZ51, blk.conv_5_1[0], grads, f"{name}conv_5_1.0", True)
         if not on("dgrad", "conv_5_1.0"):          # (likewise one tensor: dx)
-            return None
+            return None, None
         dx = buf(64)
         self._dgrad(c, DZ31, blk.conv_3_1[0], 0, 64, dx, 64, 0, res=dpre)
         virtual = mask_input and s.X.scale is not None
         am = new_amax()
-        self._dgrad(c, DZ51, blk.conv_5_1[0], 0, 64, dx, 64, 0, res=Act(dx, 64, 0, 64),
-                    mask=s.X if mask_input else None, bn=virtual and ("bn_bwd_finalize", in_bn) in c.live,
-                    out_amax=None if virtual else am)
-        return Act(dx, 64, 0, 64, amax=am)
+        e = self._dgrad(c, DZ51, blk.conv_5_1[0], 0, 64, dx, 64, 0, res=Act(dx, 64, 0, 64),
+                        mask=s.X if mask_input else None, bn=virtual and ("bn_bwd_finalize", in_bn) in c.live,
+                        out_amax=None if virtual else am)
+        return Act(dx, 64, 0, 64, amax=am), e
 
     # ------------------------------------------------------------------ backward
     def _want_default(self, named):
@@ -926,23 +884,15 @@ class TrainEngine:
         if on("head_bwd", "output_layer.2"):
             ns = max(1, min(B * (8 if H > 64 else 1), 2048))     # (image split, row band) entries: ~8 resident workgroups per CU
             wslab = torch.empty(ns * 128 * 9, dtype=torch.float32, device=dev)
-            if self.io16:
-                call("tsr_head_bwd_b16", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
-                     ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), ptr(wslab), _I(ns), _I(B), _I(H), _I(W),
-                     stream())
-            else:
-                call("tsr_head_bwd", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
-                     ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), ptr(wslab), _I(ns), _I(B), _I(H), _I(W),
-                     ptr(am_dzh0), stream())
+            self._twin("tsr_head_bwd", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
+                       ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), ptr(wslab), _I(ns), _I(B), _I(H), _I(W),
+                       amax=(am_dzh0,))
             gw = grads.dest("output_layer.2.weight", m.output_layer[2].weight.shape)
             call("tsr_reduce_splits", ptr(wslab), ptr(gw), _L(128 * 9), _I(ns), _F(1.0), stream())
             grads.put("output_layer.2.weight", gw)
-        elif self.io16:       # ("head_dgrad", "output_layer.2"): the head weight is frozen, dz_h0 is still consumed
-            call("tsr_head_dgrad_b16", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
-                 ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), _I(B), _I(H), _I(W), stream())
-        else:
-            call("tsr_head_dgrad", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
-                 ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), _I(B), _I(H), _I(W), ptr(am_dzh0), stream())
+        else:       # ("head_dgrad", "output_layer.2"): the head weight is frozen, dz_h0 is still consumed
+            self._twin("tsr_head_dgrad", ptr(dout), ptr(c.out), ptr(c.h0), _I(128), _I(128),
+                       ptr(m.output_layer[2].weight.detach()), ptr(dz_h0), _I(128), _I(B), _I(H), _I(W), amax=(am_dzh0,))
         DZ = Act(dz_h0, 128, 0, 128, amax=am_dzh0)
         HC = Act(c.hcat, 128, 0, 128, amax=c.am_hcat)
         self._wgrad(c, HC, DZ, m.output_layer[0], grads, "output_layer.0", False)
@@ -964,13 +914,8 @@ class TrainEngine:
                                      new_amax, buf)
         if on("stem_wgrad", "input_layer_force.1"):
             ns = max(1, min(B, 2048))     # image splits: ~8 resident workgroups per CU hide the load latency
-            sslab = torch.empty(ns * 64 * 27, dtype=torch.float32, device=dev)
-            call("tsr_stem_wgrad_b16" if self.io16 else "tsr_stem_wgrad", ptr(c.x), _I(c.x.shape[1]), _I(0), _I(c.hin),
-                 _I(c.win), _I(m.scale_factor), ptr(dpre.buf), _I(dpre.ctot), _I(dpre.coff), ptr(sslab), _I(ns), _I(B),
-                 stream())
-            gw = grads.dest("input_layer_force.1.weight", m.input_layer_force[1].weight.shape)
-            call("tsr_reduce_splits", ptr(sslab), ptr(gw), _L(64 * 27), _I(ns), _F(1.0), stream())
-            grads.put("input_layer_force.1.weight", gw)
+            self._stem_wgrad(c, "input_layer_force.1.weight", m.input_layer_force[1].weight, 0, dpre.buf, dpre.ctot, dpre.coff,
+                             ns, grads)
         if on("stem_dgrad", "input_layer_force.1"):
             self._stem_dgrad(c, m.input_layer_force[1].weight, dpre.buf, dpre.ctot, dpre.coff, dx, 0, 0)
 
@@ -978,12 +923,12 @@ class TrainEngine:
         dpre = Act(g_hcat, 128, 64, 64, amax=am_ghcat)
         for i in reversed(range(len(c.blocks))):
             if dpre is not None:
-                dpre = self._msrb_bwd(c, c.blocks[i], m.patternFeatureExtra_layer[i], f"patternFeatureExtra_layer.{i}", dpre,
-                                      grads, new_amax, buf, tag=f"msrb{i}", in_bn="inputContact_layer.1")
+                dpre, e = self._msrb_bwd(c, c.blocks[i], m.patternFeatureExtra_layer[i], f"patternFeatureExtra_layer.{i}", dpre,
+                                         grads, new_amax, buf, tag=f"msrb{i}", in_bn="inputContact_layer.1")
         if dpre is None:          # nothing at or below the first MSRB's input wants a gradient
             return grads.finalize()
         # X of block 0 is the fuse conv's relu(bn(zf)): finish its BN backward -> dzf
-        self._bn_bwd(c, "inputContact_layer.1", dpre.buf, 64, 0, Act(c.zf, 64, 0, 64), 0, 64, c.bnf, None, grads, "",
+        self._bn_bwd(c, "inputContact_layer.1", dpre.buf, 64, 0, Act(c.zf, 64, 0, 64), 0, 64, c.bnf, grads, e,
                      out_amax=dpre.amax, gnames=("inputContact_layer.1.weight", "inputContact_layer.1.bias"))
         AT = Act(c.catT, 64 * T, 0, 64 * T, c.bn2[0], c.bn2[1], c.bn2[2], c.bn2[3], amax=c.am_catT)
         self._wgrad(c, AT, dpre, m.inputContact_layer[0], grads, "inputContact_layer.0", False)
@@ -995,10 +940,11 @@ class TrainEngine:
                 continue
             mk = Act(c.catT, 64 * T, o, 64, c.bn2[0, o:o + 64], c.bn2[1, o:o + 64], c.bn2[2, o:o + 64],
                      c.bn2[3, o:o + 64])
-            self._dgrad(c, dpre, m.inputContact_layer[0], o, 64, gT, 64 * T, o, mask=mk, bn=on("bn_bwd_finalize", name + ".5"))
+            e = self._dgrad(c, dpre, m.inputContact_layer[0], o, 64, gT, 64 * T, o, mask=mk,
+                            bn=on("bn_bwd_finalize", name + ".5"))
             am_gT = new_amax()
-            self._bn_bwd(c, name + ".5", gT, 64 * T, o, Act(c.catT, 64 * T, 0, 64 * T), o, 64, c.bn2[:, o:o + 64], None, grads,
-                         "", out_amax=am_gT, gnames=(name + ".5.weight", name + ".5.bias"))
+            self._bn_bwd(c, name + ".5", gT, 64 * T, o, Act(c.catT, 64 * T, 0, 64 * T), o, 64, c.bn2[:, o:o + 64], grads, e,
+                         out_amax=am_gT, gnames=(name + ".5.weight", name + ".5.bias"))
             DZ2 = Act(gT, 64 * T, o, 64, amax=am_gT)
             v1 = c.bn1[t]
             A1 = Act(c.z1[t], 64, 0, 64, v1[0], v1[1], v1[2], v1[3], amax=c.am_z1[t])
@@ -1006,37 +952,41 @@ class TrainEngine:
             if not on("dgrad", name + ".4"):
                 continue
             g1 = buf(64)
-            self._dgrad(c, DZ2, seq[4], 0, 64, g1, 64, 0, mask=A1, bn=on("bn_bwd_finalize", name + ".2"))
-            self._bn_bwd(c, name + ".2", g1, 64, 0, Act(c.z1[t], 64, 0, 64), 0, 64, v1, None, grads, "",
+            e = self._dgrad(c, DZ2, seq[4], 0, 64, g1, 64, 0, mask=A1, bn=on("bn_bwd_finalize", name + ".2"))
+            self._bn_bwd(c, name + ".2", g1, 64, 0, Act(c.z1[t], 64, 0, 64), 0, 64, v1, grads, e,
                          gnames=(name + ".2.weight", name + ".2.bias"))
             if on("stem_wgrad", name + ".1"):
                 ns = max(1, min(B * (8 if H > 64 else 1), 2048))     # (image split, row band) entries
-                sslab = torch.empty(ns * 64 * 27, dtype=torch.float32, device=dev)
-                call("tsr_stem_wgrad_b16" if self.io16 else "tsr_stem_wgrad", ptr(c.x), _I(c.x.shape[1]),
-                     _I(m.axisCnt * t), _I(c.hin), _I(c.win), _I(m.scale_factor), ptr(g1), _I(64), _I(0), ptr(sslab),
-                     _I(ns), _I(B), stream())
-                gw = grads.dest(name + ".1.weight", seq[1].weight.shape)
-                call("tsr_reduce_splits", ptr(sslab), ptr(gw), _L(64 * 27), _I(ns), _F(1.0), stream())
-                grads.put(name + ".1.weight", gw)
+                self._stem_wgrad(c, name + ".1.weight", seq[1].weight, m.axisCnt * t, g1, 64, 0, ns, grads)
             if on("stem_dgrad", name + ".1"):
                 self._stem_dgrad(c, seq[1].weight, g1, 64, 0, dx, m.axisCnt * t, int(t == 0))
         return grads.finalize()
 
+    def _stem_wgrad(self, c, gname, weight, x_coff, dz, dz_ctot, dz_coff, ns, grads):
+        """The weight gradient `gname` of one stem (bilinear x sf + conv 3 -> 64 on taxel channels [x_coff, x_coff + 3)) given
+        its dz: `ns` split slabs, reduced into the gradient's slot."""
+        sslab = torch.empty(ns * 64 * 27, dtype=torch.float32, device=dz.device)
+        self._twin("tsr_stem_wgrad", ptr(c.x), _I(c.x.shape[1]), _I(x_coff), _I(c.hin), _I(c.win), _I(self.m.scale_factor),
+                   ptr(dz), _I(dz_ctot), _I(dz_coff), ptr(sslab), _I(ns), _I(c.B))
+        gw = grads.dest(gname, weight.shape)
+        call("tsr_reduce_splits", ptr(sslab), ptr(gw), _L(64 * 27), _I(ns), _F(1.0), stream())
+        grads.put(gname, gw)
+
     def _stem_dgrad(self, c, weight, dz, dz_ctot, dz_coff, dx, dx_coff, accumulate):
         """dx[:, dx_coff:dx_coff+3] (=|+=) the taxel gradient of one stem (bilinear x sf + conv 3 -> 64) given its dz."""
-        call("tsr_stem_dgrad_b16" if self.io16 else "tsr_stem_dgrad", ptr(weight.detach().contiguous()), ptr(dz),
-             _I(dz_ctot), _I(dz_coff), _I(c.hin), _I(c.win), _I(self.m.scale_factor), ptr(dx), _I(dx.shape[1]),
-             _I(dx_coff), _I(accumulate), _I(c.B), stream())
+        self._twin("tsr_stem_dgrad", ptr(weight.detach().contiguous()), ptr(dz), _I(dz_ctot), _I(dz_coff), _I(c.hin),
+                   _I(c.win), _I(self.m.scale_factor), ptr(dx), _I(dx.shape[1]), _I(dx_coff), _I(accumulate), _I(c.B))
 
 
-class TactileSRTrainFn(torch.autograd.Function):
-    """out = TactileSR_train_forward(x; params).  ``params`` are passed only so that autograd
+class TrainFn(torch.autograd.Function):
+    """out = engine.forward(x; params) of a ``TrainEngine`` (the whole network) or a ``BlockEngine`` (a standalone MSRB /
+    ResBlock); gradients for x and the parameters.  ``params`` are passed only so that autograd
     routes their gradients; the engine reads them from the module."""
 
     @staticmethod
     def forward(ctx, engine: TrainEngine, names, x, *params):
         out, c = engine.forward(x)
-        c.want_dx = bool(ctx.needs_input_grad[2])      # d loss / d taxels only when the caller's input requires grad
+        c.want_dx = bool(ctx.needs_input_grad[2])      # the input's gradient only when the caller's input requires grad
         c.want = frozenset(n for n, need in zip(names, ctx.needs_input_grad[3:]) if need)      # one flag per parameter
         ctx.engine, ctx.c, ctx.names = engine, c, names
         if any(ctx.needs_input_grad):
@@ -1060,7 +1010,7 @@ class BlockEngine(TrainEngine):
     """Train-mode forward / backward of ONE standalone ``MSRB`` or ``ResBlock`` module on an NCHW tensor (reference
     model/tactileSR_model.py:196-206,222-225 are callable modules): the same kernels and the same per-block code as the
     whole-network engine, with NCHW <-> CB16 conversion at the boundary and the gradient w.r.t. the block input
-    returned unmasked."""
+    left unmasked, as NCHW, on the context's `dx`."""
 
     def __init__(self, block, kind: str, impl: str = "fp16x3"):
         super().__init__(None, impl)
@@ -1080,7 +1030,7 @@ class BlockEngine(TrainEngine):
         B, C, H, W = x.shape
         dev = x.device
         c = self._new_ctx(B, H, W, dev)
-        c.want = self._want_default(self.block.named_parameters())      # (BlockTrainFn: what autograd asks for instead)
+        c.want = self._want_default(self.block.named_parameters())      # (TrainFn: what autograd asks for instead)
         c.want_dx = True
         self._weight_scales(c)
         new_amax = self._amax_pool(dev)
@@ -1105,8 +1055,9 @@ class BlockEngine(TrainEngine):
         B, H, W = c.B, c.H, c.W
         c.live = {r.key for r in block_backward_plan(self.kind, c.want, c.want_dx, c.bn_eval)}
         grads = GradSink(self, dict(self.block.named_parameters()), dev, token=c, want=c.want)
+        c.dx = None
         if not c.live:
-            return None, grads.finalize()
+            return grads.finalize()
         new_amax = self._amax_pool(dev)
 
         def buf(ch):
@@ -1120,32 +1071,9 @@ class BlockEngine(TrainEngine):
             am.copy_(d.abs().amax())
         dpre = Act(d, 64, 0, 64, amax=am)
         if self.kind == "msrb":
-            dx = self._msrb_bwd(c, c.s, self.block, "", dpre, grads, new_amax, buf, mask_input=False)
+            dx, _ = self._msrb_bwd(c, c.s, self.block, "", dpre, grads, new_amax, buf, mask_input=False)
         else:
             dx = self._res_bwd(c, c.s, self.block, "", dpre, grads, new_amax, buf, mask_input=False)
-        return from_cb16(dx.buf, B, 64, H, W) if dx is not None else None, grads.finalize()
-
-
-class BlockTrainFn(torch.autograd.Function):
-    """y = block(x) for a standalone MSRB / ResBlock in train mode; gradients for x and the block's parameters."""
-
-    @staticmethod
-    def forward(ctx, engine: BlockEngine, names, x, *params):
-        out, c = engine.forward(x)
-        c.want_dx = bool(ctx.needs_input_grad[2])      # the block input's gradient only when it is asked for
-        c.want = frozenset(n for n, need in zip(names, ctx.needs_input_grad[3:]) if need)
-        ctx.engine, ctx.c, ctx.names = engine, c, names
-        if any(ctx.needs_input_grad):
-            from ..ddp import note_forward
-            note_forward(engine, c)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        c = ctx.c
-        dx, grads = ctx.engine.backward(c, dout)
-        ctx.c = None
-        missing = [n for n in ctx.names if n in c.want and n not in grads]
-        if missing:
-            raise _lib.TactileSRHipError(f"backward produced no gradient for {missing[:4]}...")
-        return (None, None, dx) + tuple(grads.get(n) if n in c.want else None for n in ctx.names)
+        if dx is not None:
+            c.dx = from_cb16(dx.buf, B, 64, H, W)
+        return grads.finalize()

@@ -67,7 +67,23 @@ def _reapply_hold(root: nn.Module) -> None:
             m.training = False
 
 
-class _StandaloneBlock(nn.Module):
+class _PlanCache:
+    """Repack when a parameter changed: `_get_plan()` is the class's `_build_plan()`, built again whenever one of its
+    `_plan_fields` attributes, a parameter or a buffer (address or version) or the library's parameter epoch has moved."""
+    _plan_fields = ("conv_impl",)
+
+    def _param_key(self):
+        return tuple(getattr(self, f) for f in self._plan_fields) + (_lib.param_epoch(),) + tuple(
+            (t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+
+    def _get_plan(self):
+        key = self._param_key()
+        if self._plan is None or key != self._plan_key:
+            self._plan, self._plan_key = self._build_plan(), key
+        return self._plan
+
+
+class _StandaloneBlock(_PlanCache, nn.Module):
     """Shared forward of the standalone ``MSRB`` / ``ResBlock`` modules (the whole-network engine of ``TactileSR`` runs
     the same kernels on its own buffers): ``block(x)`` with x ``(B, 64, H, W)`` fp32 NCHW on a ROCm device.  Eval mode
     runs the inference launches (fp16x3 by default: stage-1 pair kernel, fused 1x1) and returns a plain tensor; train
@@ -88,16 +104,6 @@ class _StandaloneBlock(nn.Module):
         super().train(mode)
         _reapply_hold(self)          # hold_bn_statistics: marked BatchNorm layers stay in eval mode
         return self
-
-    def _param_key(self):
-        return (self.conv_impl, _lib.param_epoch()) + tuple((t.data_ptr(), t._version)
-                                                            for t in list(self.parameters()) + list(self.buffers()))
-
-    def _get_plan(self):
-        key = self._param_key()
-        if self._plan is None or key != self._plan_key:
-            self._plan, self._plan_key = self._build_plan(), key
-        return self._plan
 
     def block_engine(self):
         if self.train_impl not in ("fp16x3", "bf16x6", "f32"):
@@ -121,10 +127,10 @@ class _StandaloneBlock(nn.Module):
             raise _lib.TactileSRHipError(f"standalone {type(self).__name__}: conv_impl {self.conv_impl!r} is not available "
                                          "(fp16x3, bf16x6, f32)")
         if self.training:
-            from ._train import BlockTrainFn
+            from ._train import TrainFn
             named = list(self.named_parameters())
             xin = x.float().contiguous()
-            return BlockTrainFn.apply(self.block_engine(), [n for n, _ in named], xin, *[p for _, p in named])
+            return TrainFn.apply(self.block_engine(), [n for n, _ in named], xin, *[p for _, p in named])
         x = x.detach().float().contiguous()
         with torch.no_grad():
             return self._eval_forward(x)
@@ -239,6 +245,55 @@ class _timed:
         return False
 
 
+def _twin_args(io16, name, args, amax=()):
+    """`call` arguments, but for the stream, of a glue launch that has an fp32 and a bf16-storage form: `name + "_b16"` under
+    bf16 storage, else `name` -- which also takes the tensors in `amax` (the max|.| slot of what it writes) where the fp32
+    form has that one more pointer."""
+    return (name + "_b16", *args) if io16 else (name, *args, *map(ptr, amax))
+
+
+def _pack_form(ns, out, cin, ks, dgrad=False, dev_amax=False):
+    """The weight pack of arithmetic `ns` for a conv with `out` output and `cin` input channels (a data-gradient pack,
+    `dgrad`: of the flipped conv, (out, cin) = (nprime, cout)): its entry point, the packed element count and dtype, and
+    the arguments the entry point takes between the integers and the stream, but for the fp16 scale.  fp16 planes are
+    scaled by a host float, or (`dev_amax`) from a device scalar max|w|."""
+    name = "tsr_pack_conv_weight_dgrad" if dgrad else "tsr_pack_conv_weight"
+    lib = _lib.load()
+    if ns == NS_B16K:         # bf16 activation storage, the launch runs csrc/conv_b16k.hip: that kernel's slab layout
+        return name + "_b16k", lib.tsr_conv_weight_b16k_elems(out, cin, ks), torch.bfloat16, ()
+    if ns == NS_F16X3:
+        return (name + ("_f16s_dev" if dev_amax else "_f16s"), lib.tsr_conv_weight_bf16s_elems(out, cin, ks, 2),
+                torch.float16, ())
+    if ns == NS_F32:
+        return name, out * cin * ks * ks, torch.float32, ()
+    ns = 1 if ns == NS_B16 else ns      # bf16 activation storage: the weights are the one-plane bf16 pack
+    return name + "_bf16s", lib.tsr_conv_weight_bf16s_elems(out, cin, ks, ns), torch.bfloat16, (_I(ns),)
+
+
+def _pack_pair_b16k(w3, w5):
+    """bf16 storage: the weights of conv_3_1 || conv_5_1 as ONE 5x5 conv to 128 channels on conv_b16k (the 3x3 weight
+    zero-padded into the inner taps of its half; the kernel skips the others)."""
+    cin = w3.shape[1]
+    w = torch.cat([torch.nn.functional.pad(w3, (1, 1, 1, 1)), w5], 0).contiguous()
+    wp = torch.empty(_lib.load().tsr_conv_weight_b16k_pair_elems(cin), dtype=torch.bfloat16, device=w.device)
+    call("tsr_pack_conv_weight_b16k_pair", ptr(w), ptr(wp), _I(cin), stream())
+    return wp
+
+
+def _pack_host(w, ns):
+    """Pack the (cout, cin, ks, ks) weight `w` for an eval launch of arithmetic `ns`: (packed weight, w_inv_scale) -- fp16
+    planes are scaled by the power of two the host derives from max|w|, everything else is not scaled."""
+    cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
+    name, n, dtype, tail = _pack_form(ns, cout, cin, ks)
+    inv = 1.0
+    if ns == NS_F16X3:
+        wscale = _pow2_wscale(float(w.abs().max()))
+        tail, inv = (_lib.c_float(wscale),), 1.0 / wscale
+    wp = torch.empty(n, dtype=dtype, device=w.device)
+    call(name, ptr(w), ptr(wp), _I(cout), _I(cin), _I(ks), *tail, stream())
+    return wp, inv
+
+
 class _PackedConv:
     """Device-side constants of one conv launch: packed weight, folded scale/shift."""
     __slots__ = ("w", "scale", "shift", "cin", "cout", "ks", "nsplit", "w_inv_scale", "io16", "b16k")
@@ -250,31 +305,12 @@ class _PackedConv:
         w = w.contiguous()
         self.cout, self.cin, self.ks = w.shape[0], w.shape[1], w.shape[2]
         self.nsplit = nsplit
-        self.w_inv_scale = 1.0
         self.io16 = nsplit == CONV_IMPLS["bf16"]
         # bf16 activation storage (one plane is only ever that path's): the 3x3 / 5x5 convs run csrc/conv_b16k.hip
         # (its 64-channel instantiations -- 16 MFMAs per barrier step -- measure slower than the 32x32x16 kernel's 3-tap steps:
         #  3x3 64->64 0.83 vs 0.70 ms per launch at B = 4096; they stay on that kernel)
         self.b16k = self.io16 and self.ks > 1 and self.cin % 32 == 0 and self.cout == 128
-        if self.b16k:
-            n = _lib.load().tsr_conv_weight_b16k_elems(self.cout, self.cin, self.ks)
-            self.w = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-            call("tsr_pack_conv_weight_b16k", ptr(w), ptr(self.w), _I(self.cout), _I(self.cin), _I(self.ks), stream())
-        elif nsplit == NS_F16X3:
-            wscale = _pow2_wscale(float(w.abs().max()))
-            self.w_inv_scale = 1.0 / wscale
-            n = _lib.load().tsr_conv_weight_bf16s_elems(self.cout, self.cin, self.ks, 2)
-            self.w = torch.empty(n, dtype=torch.float16, device=w.device)
-            call("tsr_pack_conv_weight_f16s", ptr(w), ptr(self.w), _I(self.cout), _I(self.cin), _I(self.ks),
-                 _lib.c_float(wscale), stream())
-        elif nsplit == NS_F32:
-            self.w = torch.empty_like(w)
-            call("tsr_pack_conv_weight", ptr(w), ptr(self.w), _I(self.cout), _I(self.cin), _I(self.ks), stream())
-        else:
-            n = _lib.load().tsr_conv_weight_bf16s_elems(self.cout, self.cin, self.ks, nsplit)
-            self.w = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-            call("tsr_pack_conv_weight_bf16s", ptr(w), ptr(self.w), _I(self.cout), _I(self.cin), _I(self.ks),
-                 _I(nsplit), stream())
+        self.w, self.w_inv_scale = _pack_host(w, NS_B16K if self.b16k else nsplit)
         self.scale, self.shift = _fold(conv.bias, bn, self.cout, w.device)
 
 
@@ -323,12 +359,9 @@ class _PackedPairB16:
         w3 = seq3[0].weight.detach().float()
         w5 = seq5[0].weight.detach().float()
         self.cin = w3.shape[1]
-        w = torch.cat([torch.nn.functional.pad(w3, (1, 1, 1, 1)), w5], dim=0).contiguous()
-        n = _lib.load().tsr_conv_weight_b16k_pair_elems(self.cin)
-        self.w = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-        call("tsr_pack_conv_weight_b16k_pair", ptr(w), ptr(self.w), _I(self.cin), stream())
-        s3, sh3 = _fold(seq3[0].bias, seq3[1], 64, w.device)
-        s5, sh5 = _fold(seq5[0].bias, seq5[1], 64, w.device)
+        self.w = _pack_pair_b16k(w3, w5)
+        s3, sh3 = _fold(seq3[0].bias, seq3[1], 64, w3.device)
+        s5, sh5 = _fold(seq5[0].bias, seq5[1], 64, w3.device)
         self.scale = torch.cat([s3, s5]).contiguous()
         self.shift = torch.cat([sh3, sh5]).contiguous()
 
@@ -344,11 +377,7 @@ class _PackedHalf:
             self.w = torch.empty(64 * 128, dtype=torch.bfloat16, device=w.device)
             call("tsr_pack_w2_b16k", ptr(w), ptr(self.w), stream())
             return
-        wscale = _pow2_wscale(float(w.abs().max()))
-        self.w_inv_scale = 1.0 / wscale
-        n = _lib.load().tsr_conv_weight_bf16s_elems(64, 128, 1, 2)
-        self.w = torch.empty(n, dtype=torch.float16, device=w.device)
-        call("tsr_pack_conv_weight_f16s", ptr(w), ptr(self.w), _I(64), _I(128), _I(1), _lib.c_float(wscale), stream())
+        self.w, self.w_inv_scale = _pack_host(w, NS_F16X3)
 
 
 def _fold(bias, bn: Optional[nn.BatchNorm2d], cout: int, device):
@@ -487,13 +516,14 @@ def _run_res(p: _ResPlan, prof, src, s_in, dst, d_ctot, d_coff, s_out, f1, slot,
           amax_out=s_out)
 
 
-class TactileSR(nn.Module):
+class TactileSR(_PlanCache, nn.Module):
     """STSR / MTSR taxel super-resolution network on MI355X.
 
     ``model(LR)`` with LR ``(B, seqsCnt*axisCnt, 4, 4)`` fp32 on a ROCm device returns
     ``(B, 1, 4*scale_factor, 4*scale_factor)``, numerically equal (<=1e-5 relative) to
     the reference forward (model/tactileSR_model.py:67-84).
     """
+    _plan_fields = ("conv_impl", "head_impl", "fuse_1x1", "fuse_pair")
 
     def __init__(self, scale_factor=10, seqsCnt=1, axisCnt=3, patternFeatureExtraLayerCnt=6,
                  forceFeatureExtraLayerCnt=1, *, conv_impl: str = "fp16x3", train_impl: str = "fp16x3"):
@@ -562,10 +592,6 @@ class TactileSR(nn.Module):
         return self
 
     # ------------------------------------------------------------------ engine
-    def _param_key(self):
-        return (self.conv_impl, self.head_impl, self.fuse_1x1, self.fuse_pair, _lib.param_epoch()) + tuple((t.data_ptr(), t._version)
-                                         for t in list(self.parameters()) + list(self.buffers()))
-
     def _build_plan(self):
         """Pack weights / fold eval-mode BN once per parameter version."""
         plan: Dict[str, object] = {}
@@ -593,13 +619,6 @@ class TactileSR(nn.Module):
         plan["head_w"] = self.output_layer[2].weight.detach().float().contiguous()
         return plan
 
-    def _get_plan(self):
-        key = self._param_key()
-        if self._plan is None or key != self._plan_key:
-            self._plan = self._build_plan()
-            self._plan_key = key
-        return self._plan
-
     def _infer_pass(self, x: torch.Tensor, out: torch.Tensor, stages=None) -> None:
         """Eval-mode forward of one batch slice; mirrors reference forward :67-84."""
         plan = self._get_plan()
@@ -617,12 +636,9 @@ class TactileSR(nn.Module):
             return torch.empty(B * c * HW, dtype=torch.bfloat16 if io16 else torch.float32, device=dev)
 
         def stem(coff, w1, s1, sh1, dst, slot_):
-            if io16:
-                call("tsr_stem_fwd_b16", ptr(x), _I(ctot), _I(coff), _I(A), _I(hin), _I(win), _I(sf), ptr(w1), ptr(s1),
-                     ptr(sh1), ptr(dst), _I(64), _I(0), _I(1), _I(B), stream())
-            else:
-                call("tsr_stem_fwd", ptr(x), _I(ctot), _I(coff), _I(A), _I(hin), _I(win), _I(sf), ptr(w1), ptr(s1),
-                     ptr(sh1), ptr(dst), _I(64), _I(0), _I(1), _I(B), ptr(slot_), stream())
+            call(*_twin_args(io16, "tsr_stem_fwd", (ptr(x), _I(ctot), _I(coff), _I(A), _I(hin), _I(win), _I(sf), ptr(w1),
+                                                    ptr(s1), ptr(sh1), ptr(dst), _I(64), _I(0), _I(1), _I(B)), (slot_,)),
+                 stream())
 
         ctot = x.shape[1]
         prof = self._profile
@@ -682,8 +698,8 @@ class TactileSR(nn.Module):
         if stages is not None:
             stages["force"] = (hcat, 128, 0)
             stages["head0"] = (h0, 128, 0)
-        call("tsr_head_fwd_b16" if io16 else "tsr_head_fwd", ptr(h0), _I(128), _I(128), ptr(plan["head_w"]), ptr(out),
-             _I(1), _I(B), _I(H), _I(W), stream())
+        call(*_twin_args(io16, "tsr_head_fwd", (ptr(h0), _I(128), _I(128), ptr(plan["head_w"]), ptr(out), _I(1), _I(B), _I(H),
+                                                _I(W))), stream())
 
     def forward(self, x):
         assert x.shape[1] == self.seqsCnt * self.axisCnt, "input channel should be same with seqsCnt x axisCnt!"
@@ -692,11 +708,10 @@ class TactileSR(nn.Module):
                                          "its input to a ROCm device (no CPU fallback)")
         if self.training:
             # batch-statistics BatchNorm + autograd through the HIP backward (model/_train.py)
-            from ._train import TactileSRTrainFn
+            from ._train import TrainFn
             named = list(self.named_parameters())
             # (not detached: with LR.requires_grad_() autograd routes d loss / d taxels back through .float() / slicing)
-            out = TactileSRTrainFn.apply(self.train_engine(), [n for n, _ in named],
-                                         x.float().contiguous(), *[p for _, p in named])
+            out = TrainFn.apply(self.train_engine(), [n for n, _ in named], x.float().contiguous(), *[p for _, p in named])
             self._plan = None      # running statistics were updated in place by the kernels
             return out
         x = x.detach().float().contiguous()
@@ -757,7 +772,7 @@ class TactileSR(nn.Module):
         return out, stages
 
 
-class TactileSRCNN(nn.Module):
+class TactileSRCNN(_PlanCache, nn.Module):
     """``TactileSRCNN`` of the reference (model/tactileSR_model.py:101-153): bilinear x10 -> three conv3x3+BN+ReLU
     (3->64, 64->64, 64->64) -> six MSRBs -> conv 64->1 + ReLU.  Both reference trainers import the name
     (train/tactileSR_train.py:24, train/tactileSRSeqs_train.py:24) and none instantiates it; it is exported so that
@@ -782,18 +797,13 @@ class TactileSRCNN(nn.Module):
     def extra_repr(self):
         return f"arithmetic: eval conv_impl={self.conv_impl!r} (train mode not available)"
 
-    def _get_plan(self):
-        key = (self.conv_impl, _lib.param_epoch()) + tuple((t.data_ptr(), t._version)
-                                                           for t in list(self.parameters()) + list(self.buffers()))
-        if self._plan is None or key != self._plan_key:
-            ns = CONV_IMPLS[self.conv_impl]
-            z = self.input_zyx
-            s1, sh1 = _fold(None, z[1], 64, z[0].weight.device)
-            self._plan = (z[0].weight.detach().float().contiguous(), s1, sh1, _PackedConv(z[3], z[4], ns),
-                          _PackedConv(z[6], z[7], ns), [_msrb_plan(blk, ns, True, True, False) for blk in self.msrb_layer],
-                          self.output[0].weight.detach().float().contiguous())
-            self._plan_key = key
-        return self._plan
+    def _build_plan(self):
+        ns = CONV_IMPLS[self.conv_impl]
+        z = self.input_zyx
+        s1, sh1 = _fold(None, z[1], 64, z[0].weight.device)
+        return (z[0].weight.detach().float().contiguous(), s1, sh1, _PackedConv(z[3], z[4], ns),
+                _PackedConv(z[6], z[7], ns), [_msrb_plan(blk, ns, True, True, False) for blk in self.msrb_layer],
+                self.output[0].weight.detach().float().contiguous())
 
     def forward(self, x):
         if not x.is_cuda:

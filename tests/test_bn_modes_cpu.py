@@ -284,13 +284,15 @@ class _DryRun:
         from tactilesr_amd.model import _train, tactileSR_model
         self.mods = (_train, tactileSR_model)
         self.saved = [(m, k, getattr(m, k)) for m in self.mods for k in ("call", "ptr", "stream", "conv_ex") if hasattr(m, k)]
-        self.names, self.conv = Counter(), []
+        self.names, self.conv, self.trace = Counter(), [], []          # trace: every launch in order, with its arguments
 
         def call(name, *args):
             self.names[name] += 1
+            self.trace.append((name, args))
 
         def conv_ex(**kw):
             self.conv.append(kw)
+            self.trace.append(("conv_ex", kw))
 
         for m in self.mods:
             m.call, m.ptr, m.stream = call, (lambda t: ctypes.c_void_p(0)), (lambda: ctypes.c_void_p(0))
@@ -382,6 +384,48 @@ def test_engine_host_code_follows_the_held_layers(pattern, impl):
     assert epi1 == exp_epi1, (epi1, exp_epi1)
 
 
+@pytest.mark.parametrize("impl", ["fp16x3", "bf16", "f32"])
+def test_statistics_are_reduced_over_the_entries_of_the_launch_that_wrote_them(impl):
+    """Every launch that leaves per-workgroup sums in the statistics slab is followed by a finalize over exactly the entries
+    the library reports for the form (`nsplit`) that was launched.  B = 5: a form with 2 images per workgroup and one with 4
+    differ there (6 and 8 entries per tile), at B = 3 they would not.  One layer is held so that both backward finalizes run."""
+    import tactilesr_amd
+    from tactilesr_amd import _lib
+    torch.manual_seed(5)
+    m = tactilesr_amd.TactileSR(3, 2, 3, 2, 1).train()
+    m.train_impl = impl
+    m.patternFeatureExtra_layer[0].conv_3_2[1].eval()
+    B, H, W = 5, 12, 12
+    eng = m.train_engine()
+    with _DryRun() as dry, torch.no_grad():
+        out, c = eng.forward(torch.rand(B, 6, 4, 4))
+        eng.backward(c, torch.ones_like(out))
+    assert out.shape == (B, 1, H, W)
+    want = lambda kw: _lib.load().tsr_conv2d_slab_entries_ex(B, H, W, kw["cout"], kw["ks"], kw["nsplit"])
+
+    def following(i, names):
+        for name, args in dry.trace[i + 1:]:
+            assert name != "conv_ex", "no finalize between two conv launches"
+            if name in names:
+                return name, args
+
+    seen = Counter()
+    for i, (name, kw) in enumerate(dry.trace):
+        if name != "conv_ex":
+            continue
+        if kw.get("epi_mode") == 1:
+            fin, args = following(i, ("tsr_bn_stats_finalize",))
+            assert args[2].value == want(kw), (kw["cout"], kw["ks"], kw["nsplit"])
+            seen[fin] += 1
+        if kw.get("bn"):
+            fin, args = following(i, ("tsr_bn_bwd_finalize", "tsr_bn_bwd_finalize_eval"))
+            assert args[1].value == want(kw), (kw["cout"], kw["ks"], kw["nsplit"])
+            seen[fin] += 1
+    pair = 2 if impl == "bf16" else 0
+    assert seen == Counter(tsr_bn_stats_finalize=2 + 1 + 4 * 2 - 1 - pair, tsr_bn_bwd_finalize=2 * 3 + 1 + 2 * 2 - 1,
+                           tsr_bn_bwd_finalize_eval=1)
+
+
 @pytest.mark.parametrize("held", [("conv_3_1.1", "conv_5_1.1", "conv_3_2.1", "conv_5_2.1"), ("conv_5_1.1", "conv_3_2.1")])
 def test_block_engine_inherits_the_behaviour(held):
     from tactilesr_amd.model.tactileSR_model import MSRB
@@ -395,7 +439,8 @@ def test_block_engine_inherits_the_behaviour(held):
         out, c = eng.forward(torch.rand(2, 64, 6, 6))
         fwd = Counter(dry.names)
         dry.names.clear()
-        dx, grads = eng.backward(c, torch.ones_like(out))
+        grads = eng.backward(c, torch.ones_like(out))
+        dx = c.dx
     assert c.bn_eval == frozenset(held)
     assert fwd["tsr_bn_eval_vectors"] == len(held) and fwd.get("tsr_bn_stats_finalize", 0) == 4 - len(held)
     plan = block_backward_plan("msrb", c.want, True, bn_eval=held)

@@ -527,7 +527,8 @@ def test_block_engine_host_code_follows_the_plan(kind, frozen, x_grad):
         assert c.want == want and c.want_dx is True
         c.want_dx = x_grad
         dry.counts.clear()
-        dx, grads = eng.backward(c, torch.ones_like(out))
+        grads = eng.backward(c, torch.ones_like(out))
+        dx = c.dx
     assert dry.counts == FZ.expected_calls(plan, want), (dry.counts, FZ.expected_calls(plan, want))
     assert set(grads) == set(want) and (dx is not None) == x_grad
     assert eng.arena.names == FZ.production_order(plan, want)
