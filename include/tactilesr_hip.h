@@ -527,6 +527,32 @@ int tsr_adam_l2_multi_dev_clip(const tsr_adam_chunk* chunks, int n_chunks, const
 int tsr_psnr_ssim(const float* a, const float* b, int B, int n, double psnr_div, double max_value,
                   double C1, double C2, float* psnr, float* ssim, void* stream);
 
+/* Differentiable SSIM (utility/tools.py:66-81 calculationSSIM, :84-114 class SSIM "# ssim loss"): per-image SSIM of the
+ * prediction y against the target t, both (B,1,H,W) NCHW fp32 contiguous, and its gradient with respect to y, from ONE
+ * launch (csrc/ssim_loss.hip).
+ *   win = 0          the global form: one window per image with weight 1/(H*W) -- calculationSSIM's formula, the
+ *                    value tsr_psnr_ssim reports; H*W <= 2^28.
+ *   win in 3,5,..11  the windowed form: the 1-D Gaussian g[k] ~ exp(-(k - (win-1)/2)^2 / (2 sigma^2)), normalised to
+ *                    sum 1, applied separably as a VALID correlation G[.]; the map is (H-win+1) x (W-win+1);
+ *                    win <= H, W <= 128.  sigma is not read when win = 0.
+ * With x = y (the prediction):
+ *   mx = G[x], mt = G[t], sxx = G[x^2] - mx^2, stt = G[t^2] - mt^2, sxt = G[x t] - mx mt
+ *   A1 = 2 mx mt + C1, A2 = 2 sxt + C2, B1 = mx^2 + mt^2 + C1, B2 = sxx + stt + C2, S = A1 A2 / (B1 B2)
+ *   ssim[b] = mean of S over image b's map (N positions)
+ *   P = 2 mt (A2 - A1)/(B1 B2) - 2 mx S (1/B1 - 1/B2),  Q = -S/B2,  R = 2 A1/(B1 B2)
+ *   d ssim[b] / d y_p = (1/N) (G^T[P] + 2 y_p G^T[Q] + t_p G^T[R]),  G^T the adjoint (full) correlation.
+ * dy (optional; NULL = values only) (B,1,H,W):  dy = dy_scale * d ssim[b]/d y  when accumulate = 0,
+ * dy += the same when accumulate = 1 (the train step folds the term into the MSE gradient this way).
+ * All window sums, S, P, Q, R and the adjoint sums are fp64 (the moments cancel: fp32 misses 1e-5); values and gradients
+ * are rounded to fp32 once, at the store.  One workgroup per image, fixed summation order, no atomics: two launches
+ * give the same bits.  Images are independent: a NaN or Inf pixel makes its own image's ssim NaN and its gradient
+ * NaN wherever a window holds the pixel (everywhere when win = 0), as in torch; every other image is untouched.
+ * Refusals (status 1, nothing launched, ssim and dy untouched): a NULL y, t or ssim; B, H or W <= 0; win negative,
+ * even, 1 or above 11; with win > 0, H or W below win or above 128, or sigma <= 0 or NaN; H*W > 2^28 with win = 0;
+ * C1 or C2 <= 0 or NaN; accumulate not 0 or 1; dy_scale NaN. */
+int tsr_ssim_fwd_bwd(const float* y, const float* t, int B, int H, int W, int win, double sigma, double C1, double C2,
+                     float* ssim, float* dy, float dy_scale, int accumulate, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * tPSFNet (model/tPSFNet.py): batched, one workgroup per sample (the reference loops over the
  * batch in python, :118-125).  size is fixed at 100x100 depth / 99x99 PSF / 4x4 taxels, as the

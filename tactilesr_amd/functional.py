@@ -1,6 +1,6 @@
 """HIP-backed functional pieces of the SR training / eval step that sit outside the model:
-target preparation, MSE loss, PSNR / SSIM (reference train/tactileSR_train.py:41-51,66-101;
-utility/tools.py:49-81)."""
+target preparation, MSE loss, PSNR / SSIM, the differentiable SSIM and the MSE + SSIM loss (reference
+train/tactileSR_train.py:41-51,66-101; utility/tools.py:49-114)."""
 from __future__ import annotations
 
 import torch
@@ -52,6 +52,96 @@ def mse_loss(y: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     if not y.is_cuda:
         raise TactileSRHipError("mse_loss needs ROCm tensors (no CPU fallback)")
     return _MSE.apply(y.float(), target)
+
+
+def _ssim_launch(y: torch.Tensor, t: torch.Tensor, data_range, window, sigma, K1, K2, dy, dy_scale, accumulate):
+    """One ``tsr_ssim_fwd_bwd`` launch on contiguous fp32 (B,1,H,W) tensors: the per-sample values; ``dy`` (or None)
+    is written / accumulated in place."""
+    if y.dim() != 4 or y.shape[1] != 1 or t.shape != y.shape:
+        raise TactileSRHipError(f"ssim needs two (B,1,H,W) tensors of one shape, got {tuple(y.shape)} and {tuple(t.shape)}")
+    B, _, H, W = y.shape
+    vals = torch.empty(B, dtype=torch.float32, device=y.device)
+    call("tsr_ssim_fwd_bwd", ptr(y), ptr(t), _I(B), _I(H), _I(W), _I(int(window)), _D(float(sigma)),
+         _D((K1 * data_range) ** 2), _D((K2 * data_range) ** 2), ptr(vals), ptr(dy), _F(dy_scale), _I(accumulate),
+         stream())
+    return vals
+
+
+def ssim(a: torch.Tensor, b: torch.Tensor, data_range: float = 1.0, window: int = 11, sigma: float = 1.5,
+         K1: float = 0.01, K2: float = 0.03) -> torch.Tensor:
+    """Per-sample SSIM of two (B,1,H,W) batches, no autograd.  ``window`` odd in 3..11: the Gaussian-windowed form
+    (valid correlation, H, W <= 128); ``window=0``: one global window, the reference's ``calculationSSIM``
+    (utility/tools.py:66-81) -- with ``data_range=1.0`` (C1 = 0.01^2, C2 = 0.03^2) what ``psnr_ssim`` reports."""
+    if not a.is_cuda or not b.is_cuda:
+        raise TactileSRHipError("ssim needs ROCm tensors (no CPU fallback)")
+    return _ssim_launch(a.detach().float().contiguous(), b.detach().float().contiguous(), data_range, window, sigma,
+                        K1, K2, None, 0.0, 0)
+
+
+class _SSIMLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, target, data_range, window, sigma, K1, K2):
+        y = y.contiguous()
+        t = target.detach().float().contiguous()
+        dy = torch.empty_like(y)
+        vals = _ssim_launch(y, t, data_range, window, sigma, K1, K2, dy, -1.0 / y.shape[0], 0)
+        ctx.save_for_backward(dy)
+        return 1.0 - vals.mean()
+
+    @staticmethod
+    def backward(ctx, gout):
+        (dy,) = ctx.saved_tensors
+        return dy * gout, None, None, None, None, None, None
+
+
+def ssim_loss(y: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, window: int = 11, sigma: float = 1.5,
+              K1: float = 0.01, K2: float = 0.03) -> torch.Tensor:
+    """``1 - mean_b ssim_b`` (the reference's "# ssim loss", utility/tools.py:84-114, in the windowed or the global
+    form of ``ssim``): value and d loss / d y from one launch; the target gets no gradient."""
+    if not y.is_cuda or not target.is_cuda:
+        raise TactileSRHipError("ssim_loss needs ROCm tensors (no CPU fallback)")
+    return _SSIMLoss.apply(y.float(), target, data_range, window, sigma, K1, K2)
+
+
+def sr_loss_fwd_bwd(y: torch.Tensor, target: torch.Tensor, ssim_weight: float = 0.0, data_range: float = 1.0,
+                    window: int = 11, sigma: float = 1.5, K1: float = 0.01, K2: float = 0.03, return_parts: bool = False):
+    """``MSE(y, target) + ssim_weight * (1 - mean_b ssim_b)`` and its gradient w.r.t. ``y``, outside autograd:
+    ``(loss (1,), dy)``.  The MSE launch, then the SSIM launch accumulating ``-ssim_weight / B * d ssim_b / d y`` into
+    the same ``dy``.  ``ssim_weight == 0`` is ``mse_fwd_bwd``, launch for launch.  ``return_parts=True`` appends the
+    two terms: ``(loss, dy, mse (1,), ssim (B,) or None)``."""
+    if not y.is_cuda or not target.is_cuda:
+        raise TactileSRHipError("sr_loss_fwd_bwd needs ROCm tensors (no CPU fallback)")
+    mse, dy = mse_fwd_bwd(y, target)
+    if ssim_weight == 0:
+        return (mse, dy, mse, None) if return_parts else (mse, dy)
+    t = target.detach().float().contiguous()
+    vals = _ssim_launch(y.contiguous(), t, data_range, window, sigma, K1, K2, dy, -float(ssim_weight) / y.shape[0], 1)
+    loss = mse + float(ssim_weight) * (1.0 - vals.mean())
+    return (loss, dy, mse, vals) if return_parts else (loss, dy)
+
+
+class _SRLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, target, ssim_weight, data_range, window, sigma):
+        loss, dy, mse, vals = sr_loss_fwd_bwd(y, target, ssim_weight, data_range, window, sigma, return_parts=True)
+        ctx.save_for_backward(dy)
+        mse0 = mse[0]
+        ctx.mark_non_differentiable(mse0, vals)
+        return loss[0], mse0, vals
+
+    @staticmethod
+    def backward(ctx, gout, _gmse, _gvals):
+        (dy,) = ctx.saved_tensors
+        return dy * gout, None, None, None, None, None
+
+
+def sr_loss(y: torch.Tensor, target: torch.Tensor, ssim_weight: float, data_range: float = 1.0, window: int = 11,
+            sigma: float = 1.5):
+    """The autograd form of ``sr_loss_fwd_bwd`` for ``ssim_weight != 0``: ``(loss, mse, per-sample ssim)``; only
+    ``loss`` carries a gradient (to ``y``)."""
+    if not y.is_cuda:
+        raise TactileSRHipError("sr_loss needs ROCm tensors (no CPU fallback)")
+    return _SRLoss.apply(y.float(), target, float(ssim_weight), data_range, window, sigma)
 
 
 def psnr_ssim(a: torch.Tensor, b: torch.Tensor, maxValue: float, reference_quirk: bool = True,

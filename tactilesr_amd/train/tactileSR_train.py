@@ -29,12 +29,25 @@ def _prep(batch, config, device):
     return LR, HR
 
 
+def ssim_loss_config(config):
+    """The optional loss keys ``(ssim_loss_weight, ssim_window, ssim_sigma, ssim_data_range)``, defaults
+    ``(0.0, 11, 1.5, 1.0)``.  A weight of 0 (or no key) is the reference's loss, nn.MSELoss alone
+    (train/tactileSR_train.py:49); otherwise the loss is ``MSE + weight * (1 - mean_b ssim_b)`` with the windowed
+    (``ssim_window`` odd in 3..11) or global (``ssim_window = 0``) SSIM of ``functional.ssim``."""
+    return (float(config.get("ssim_loss_weight", 0.0)), int(config.get("ssim_window", 11)),
+            float(config.get("ssim_sigma", 1.5)), float(config.get("ssim_data_range", 1.0)))
+
+
 def train_cal_loss(model, batch, config):
     device = next(model.parameters()).device
     LR, HR = _prep(batch, config, device)
     out = model(LR)
-    loss = Fh.mse_loss(out, HR)
-    return loss, {"total_loss": loss}
+    weight, window, sigma, data_range = ssim_loss_config(config)
+    if weight == 0:
+        loss = Fh.mse_loss(out, HR)
+        return loss, {"total_loss": loss}
+    loss, mse, vals = Fh.sr_loss(out, HR, weight, data_range, window, sigma)
+    return loss, {"total_loss": loss, "mse_loss": mse, "ssim": vals.mean()}
 
 
 def fused_clip_applies(model, optimizer) -> bool:
@@ -91,11 +104,15 @@ def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite
 
 
 @torch.no_grad()
-def eval_func(model, test_loader, config):
+def eval_func(model, test_loader, config, windowed_ssim=False):
+    """The reference's three averages (loss, SSIM, PSNR).  ``windowed_ssim=True`` appends a fourth: the windowed SSIM
+    of ``functional.ssim`` with the config's ``ssim_window`` / ``ssim_sigma`` / ``ssim_data_range`` (``ssim_loss_config``),
+    averaged the same way; the first three are unchanged."""
     device = next(model.parameters()).device
     model.eval()
-    tot_loss = tot_ssim = tot_psnr = 0.0
+    tot_loss = tot_ssim = tot_psnr = tot_wssim = 0.0
     n = 0
+    _, window, sigma, data_range = ssim_loss_config(config)
     for batch in test_loader:
         LR, HR = _prep(batch, config, device)
         out = model(LR)
@@ -103,5 +120,9 @@ def eval_func(model, test_loader, config):
         ps, ss = Fh.psnr_ssim(out, HR, config["sensorMaxVaule_factor"], reference_quirk=True)
         tot_psnr += float(ps.mean())
         tot_ssim += float(ss.mean())
+        if windowed_ssim:
+            tot_wssim += float(Fh.ssim(out, HR, data_range, window, sigma).mean())
         n += 1
+    if windowed_ssim:
+        return tot_loss / n, tot_ssim / n, tot_psnr / n, tot_wssim / n
     return tot_loss / n, tot_ssim / n, tot_psnr / n

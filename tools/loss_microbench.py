@@ -1,0 +1,208 @@
+#!/usr/bin/env python3
+"""Cost of the SSIM loss term (tsr_ssim_fwd_bwd), timed with HIP events:
+    python tools/loss_microbench.py [--rounds R] [--only kernel|step] [--steps-of b32_eager] [--out profiles/ssim_loss_cost.json]
+Measures
+  kernel   the launch alone at (8192,1,40,40) and (256,1,100,100), window 11: values only, with dy (accumulating, as the
+           train step calls it), and the MSE launch pair beside it; ms per launch and the HBM bytes the launch has to
+           move over that time.
+  step     the train step (``train_one_iter``: forward + loss + backward + Adam, train_impl fp16x3, sf 10 / T 1) with
+           ssim_loss_weight 0 and 0.1: eager at B = 2048, eager at B = 32, graph-replayed (``GraphedTrainStep``) at B = 32;
+           and at B = 32 eager the same loss composed from torch ops through autograd (``torch`` below) -- what a user
+           has without the kernel.
+Every configuration of one comparison holds its own model from the same seed; all are warmed, then they alternate inside
+each of R rounds; reported are the median round and the spread (max - min) in ms, and for the steps the difference to
+weight 0 with the run's spread beside it.  Targets are contact-like blobs (the loss term is ~0 on white noise), the
+steps run at the reference's warm-up start learning rate, and a case whose output is all zero is marked invalid."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import tactilesr_amd  # noqa: E402
+import tactilesr_amd.functional as Fh  # noqa: E402
+from tactilesr_amd import optim  # noqa: E402
+from tactilesr_amd.train import tactileSR_train as TR  # noqa: E402
+from tactilesr_amd.train.graph import GraphedTrainStep  # noqa: E402
+
+LR_START = 1e-3 * 1e-4          # the reference's base lr x its warm-up factor: the first iteration's learning rate
+WEIGHT = 0.1
+KERNEL_SHAPES = ((8192, 40, 40), (256, 100, 100))
+
+
+def blobs(B, H, W, gen, amp=10.0):
+    """(B,1,H,W): three Gaussian blobs per image, the largest pixel at most `amp`."""
+    r = torch.arange(H, dtype=torch.float32)[None, :, None]
+    c = torch.arange(W, dtype=torch.float32)[None, None, :]
+    img = torch.zeros(B, H, W)
+    for _ in range(3):
+        a = 2 + 8 * torch.rand(B, 1, 1, generator=gen)
+        cr, cc = torch.rand(B, 1, 1, generator=gen) * H, torch.rand(B, 1, 1, generator=gen) * W
+        s = (0.04 + 0.08 * torch.rand(B, 1, 1, generator=gen)) * max(H, W)
+        img = img + a * torch.exp(-((r - cr) ** 2 + (c - cc) ** 2) / (2 * s * s))
+    return (img * (amp / img.amax(dim=(1, 2), keepdim=True).clamp_min(amp)))[:, None].contiguous()
+
+
+def torch_ssim(y, t, window=11, sigma=1.5, data_range=1.0):
+    """Windowed SSIM from torch ops in the tensors' dtype (the eager alternative): per-sample values.  The five
+    moments go through the separable window as ONE stacked tensor, and the window is applied with ``unfold`` views
+    and weighted sums -- torch's own element-wise and reduction kernels, no convolution library -- so the composition
+    is about as few launches as torch ops allow."""
+    k = torch.arange(window, dtype=torch.float64) - (window - 1) / 2
+    g = torch.exp(-k * k / (2 * sigma * sigma))
+    g = (g / g.sum()).to(y.dtype).to(y.device)
+    C1, C2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    z = torch.cat([y, t, y * y, t * t, y * t], dim=1)                         # (B,5,H,W)
+    z = (z.unfold(2, window, 1) * g).sum(-1)                                  # rows:    (B,5,H-w+1,W)
+    z = (z.unfold(3, window, 1) * g).sum(-1)                                  # columns: (B,5,H-w+1,W-w+1)
+    mx, mt, exx, ett, ext = z.unbind(1)
+    sxx, stt, sxt = exx - mx * mx, ett - mt * mt, ext - mx * mt
+    S = ((2 * mx * mt + C1) * (2 * sxt + C2)) / ((mx * mx + mt * mt + C1) * (sxx + stt + C2))
+    return S.mean(dim=(1, 2))
+
+
+def timed(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def alternate(fns, warmup, rounds, n):
+    """{name: [ms per call, one per round]}: every fn warmed, then the fns take turns inside each round."""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    t = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            t[k].append(timed(fn, n))
+    return t
+
+
+def kernel_cases(a):
+    cases = []
+    for B, H, W in KERNEL_SHAPES:
+        gen = torch.Generator().manual_seed(43)
+        t = blobs(B, H, W, gen).cuda()
+        y = (t + 0.5 * torch.randn(t.shape, generator=gen).cuda()).clamp_min(0).contiguous()
+        dy = torch.zeros_like(y)
+        fns = {
+            "ssim_values": lambda: Fh._ssim_launch(y, t, 1.0, 11, 1.5, 0.01, 0.03, None, 0.0, 0),
+            "ssim_with_dy": lambda: Fh._ssim_launch(y, t, 1.0, 11, 1.5, 0.01, 0.03, dy, -WEIGHT / B, 1),
+            "mse_fwd_bwd": lambda: Fh.mse_fwd_bwd(y, t),
+        }
+        rounds = alternate(fns, a.warmup, a.rounds, a.launches)
+        px = B * H * W * 4
+        moved = {"ssim_values": 2 * px, "ssim_with_dy": 5 * px, "mse_fwd_bwd": 3 * px}   # y, t (twice with dy: the adjoint rereads them) + dy read and written
+        for k, v in rounds.items():
+            med = statistics.median(v)
+            case = dict(shape=[B, 1, H, W], window=11, launch=k, ms_median=round(med, 5), ms_spread=round(max(v) - min(v), 5),
+                        rounds_ms=[round(x, 5) for x in v], bytes_moved=moved[k], gb_per_s=round(moved[k] / med / 1e6, 1))
+            cases.append(case)
+            print(f"[loss microbench] kernel ({B},1,{H},{W}) {k:13s}: {med:8.4f} ms (spread {case['ms_spread']:.4f}), "
+                  f"{case['gb_per_s']:.0f} GB/s of the bytes it has to move", flush=True)
+    return cases
+
+
+def build(weight):
+    torch.manual_seed(42)
+    m = tactilesr_amd.TactileSR().cuda().train()
+    m.train_impl = "fp16x3"
+    opt = optim.Adam(m.parameters(), lr=LR_START, weight_decay=1e-2)
+    conf = dict(TR.default_config(), ssim_data_range=10.0)
+    if weight is not None:
+        conf["ssim_loss_weight"] = weight
+    return m, opt, conf
+
+
+def torch_step(m, opt, batch, conf):
+    """train_one_iter with the SSIM term composed from torch ops (fp32) through autograd."""
+    LR, HR = TR._prep(batch, conf, "cuda")
+    out = m(LR)
+    loss = Fh.mse_loss(out, HR) + WEIGHT * (1 - torch_ssim(out, HR, data_range=conf["ssim_data_range"]).mean())
+    opt.zero_grad()
+    loss.backward()
+    opt.step()
+    return {"total_loss": loss}
+
+
+def step_cases(a):
+    cases = []
+    for B, modes in ((2048, ("eager",)), (32, ("eager", "graphed"))):
+        modes = [mode for mode in modes if a.steps_of in (None, f"b{B}_{mode}")]
+        if not modes:
+            continue
+        gen = torch.Generator().manual_seed(43)
+        batch = ((torch.rand(B, 3, 4, 4, generator=gen) * 8).cuda(), (blobs(B, 100, 100, gen) * 10).cuda())
+        for mode in modes:
+            names = ["weight_0", f"weight_{WEIGHT}"] + (["torch"] if (B, mode) == (32, "eager") else [])
+            fns, models = {}, {}
+            for name in names:
+                m, opt, conf = build(None if name == "weight_0" else (0.0 if name == "torch" else WEIGHT))
+                models[name] = m
+                if name == "torch":
+                    fns[name] = lambda m=m, opt=opt, conf=conf: torch_step(m, opt, batch, conf)
+                elif mode == "graphed":
+                    fns[name] = lambda g=GraphedTrainStep(m, opt, conf, warmup=1): g(batch)
+                else:
+                    fns[name] = lambda m=m, opt=opt, conf=conf: TR.train_one_iter(m, opt, batch, conf)
+            n = a.steps if B > 32 else a.steps * 10
+            rounds = alternate(fns, max(a.warmup, 3), a.rounds, n)
+            med = {k: statistics.median(v) for k, v in rounds.items()}
+            run_spread = max(max(v) - min(v) for v in rounds.values())
+            for name in names:
+                with torch.no_grad():
+                    models[name].eval()
+                    frac = float((models[name](batch[0][:8].float()) > 0).float().mean())
+                    models[name].train()
+                v = rounds[name]
+                case = dict(B=B, mode=mode, loss=name, ms_per_step_median=round(med[name], 4),
+                            ms_per_step_spread=round(max(v) - min(v), 4), rounds_ms=[round(x, 4) for x in v],
+                            delta_to_weight_0_ms=round(med[name] - med["weight_0"], 4), run_spread_ms=round(run_spread, 4),
+                            steps_per_round=n, out_nonzero_frac=round(frac, 5), valid=bool(frac > 0))
+                cases.append(case)
+                print(f"[loss microbench] step B={B} {mode:7s} {name:10s}: {med[name]:9.4f} ms/step (spread "
+                      f"{case['ms_per_step_spread']:.4f}), {case['delta_to_weight_0_ms']:+.4f} ms to weight 0 (run spread "
+                      f"{run_spread:.4f})" + ("" if case["valid"] else "  INVALID: the output is all zero"), flush=True)
+            del fns, models
+            torch.cuda.empty_cache()
+    return cases
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--launches", type=int, default=50, help="kernel launches per round")
+    ap.add_argument("--steps", type=int, default=5, help="train steps per round at B = 2048 (ten times as many at B = 32)")
+    ap.add_argument("--only", choices=("kernel", "step"), default=None)
+    ap.add_argument("--steps-of", choices=("b2048_eager", "b32_eager", "b32_graphed"), default=None,
+                    help="time only this step comparison")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ssim_loss_cost.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("loss_microbench: needs a ROCm device (the timing is of the GPU)")
+    result = dict(tool="tools/loss_microbench.py", device=torch.cuda.get_device_name(0), rounds=a.rounds, warmup=a.warmup,
+                  launches=a.launches, steps=a.steps, weight=WEIGHT, lr=LR_START)
+    if a.only != "step":
+        result["kernel"] = kernel_cases(a)
+    if a.only != "kernel":
+        result["step"] = step_cases(a)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(f"[loss microbench] wrote {a.out}")
+
+
+if __name__ == "__main__":
+    main()
