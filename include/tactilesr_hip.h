@@ -553,6 +553,42 @@ int tsr_psnr_ssim(const float* a, const float* b, int B, int n, double psnr_div,
 int tsr_ssim_fwd_bwd(const float* y, const float* t, int B, int H, int W, int win, double sigma, double C1, double C2,
                      float* ssim, float* dy, float dy_scale, int accumulate, void* stream);
 
+/* Pixel losses of the train step (csrc/pixel_loss.hip): MSE, L1, Charbonnier and Huber of d = y - t over n fp32 elements,
+ * with an optional contact weight, and the gradients with respect to the prediction y AND the target t from one pass.
+ * d is the exact difference of the two floats, carried in double.
+ *   kind 0  MSE          rho(d) = d^2                                                        param not read
+ *   kind 1  L1           rho(d) = |d|                           rho'(0) = sign(0) = 0        param not read
+ *   kind 2  Charbonnier  rho(d) = sqrt(d^2 + eps^2)                                          param = eps > 0
+ *   kind 3  Huber        rho(d) = d^2/2 for |d| <= delta, else delta (|d| - delta/2)         param = delta > 0
+ *                        (torch's HuberLoss; both branches agree at |d| = delta)
+ *   w_p = 1 + fg_weight [t_p > fg_threshold]   the comparison on the fp32 values (exact); a NaN target compares false
+ *   loss[0] = (1/n) sum_p w_p rho(d_p)         the divisor is n, not sum w: fg_weight = 0 is the unweighted loss, and a
+ *                                              background pixel's gradient does not depend on the batch's contact count
+ *   g_p = w_p rho'(d_p) / n
+ * dy (optional) (n):  dy = dy_scale * g when accumulate = 0,  dy += dy_scale * g when accumulate = 1 -- the contract of
+ * tsr_ssim_fwd_bwd, whose launch can keep accumulating behind this one.
+ * dt (optional) (n), always overwritten:  dt = -dy_scale * g, the exact target gradient (every loss depends on y - t only,
+ * and the weight is not differentiated).  dt and dy must not alias.
+ * Summation: fp64 in a fixed order -- one partial per workgroup into work (TSR_PIXEL_LOSS_WORK doubles), then one small
+ * launch that adds them in a fixed order; no floating-point atomics, no completion counter: two launches give the same
+ * bits.  The value and every gradient element are computed in fp64 and rounded to fp32 once, at the store (an L1 element
+ * is the fp32 rounding of +-dy_scale w / n, a linear Huber element that of +-dy_scale delta w / n).
+ * A streaming kernel (grid-stride, at most TSR_PIXEL_LOSS_WORK workgroups): 16-byte loads and stores with a scalar head
+ * and tail where y, t and the given dy, dt sit at one common offset from 16-byte alignment (any multiple of 4 bytes);
+ * pointers at different offsets are served one float at a time.
+ * Non-finite input: elements are independent.  A non-finite d_p reaches the loss and its own dy / dt element; every other
+ * gradient element keeps the bits of the clean run.  A NaN d_p gives NaN in its element for every kind (for L1 unlike
+ * torch, whose sign(NaN) is 0: a silent zero would hide a bad pixel).  d_p = +-Inf gives what the formula gives in IEEE
+ * arithmetic: MSE +-Inf, L1 +-dy_scale w / n, Huber +-dy_scale delta w / n, Charbonnier NaN.  The loss is NaN if any d_p
+ * is NaN, otherwise +Inf.
+ * Refusals (status 1, nothing launched, nothing written): a NULL y, t, loss or work; n <= 0; kind outside 0..3; kind 2 or
+ * 3 with param <= 0, NaN or Inf; fg_weight < 0, NaN or Inf; fg_threshold NaN; accumulate not 0 or 1; accumulate = 1 with
+ * dy NULL; dy_scale NaN; dt == dy when both are given. */
+#define TSR_PIXEL_LOSS_WORK 2048
+int tsr_pixel_loss_fwd_bwd(const float* y, const float* t, long long n, int kind, double param, float fg_weight,
+                           float fg_threshold, float* loss, float* dy, float dy_scale, int accumulate, float* dt,
+                           double* work, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * tPSFNet (model/tPSFNet.py): batched, one workgroup per sample (the reference loops over the
  * batch in python, :118-125).  size is fixed at 100x100 depth / 99x99 PSF / 4x4 taxels, as the

@@ -95,6 +95,7 @@ SIGNATURES = {
     "tsr_adam_l2_multi_dev_clip": [_P, _I, _P, c_double, c_double, _F, _F, _P, _P],
     "tsr_psnr_ssim": [_P, _P, _I, _I, c_double, c_double, c_double, c_double, _P, _P, _P],
     "tsr_ssim_fwd_bwd": [_P, _P, _I, _I, _I, _I, c_double, c_double, c_double, _P, _P, _F, _I, _P],
+    "tsr_pixel_loss_fwd_bwd": [_P, _P, _L, _I, c_double, _F, _F, _P, _P, _F, _I, _P, _P, _P],
     "tpsf_forward": [_P, _P, _P, _P, _P, _I, _P],
     "tpsf_backward": [_P, _P, _P, _P, _P, _P, _I, _P],
     "tpsf_backward_ex": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],

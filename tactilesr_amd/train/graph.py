@@ -20,9 +20,10 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
 * Recapture: when ``train_impl``, the parameter / buffer / optimizer-state / gradient-arena addresses, the set of
   parameters that require grad (the captured backward holds only the launches a trainable parameter depends on), the set
   of BatchNorm layers in eval mode (``hold_bn_statistics``: their statistics launches are not in the capture), the loss
-  config (the optional ``ssim_loss_weight`` / ``ssim_window`` / ``ssim_sigma`` / ``ssim_data_range`` included: the
-  captured loss is ``functional.sr_loss_fwd_bwd``, the MSE launch plus, for a non-zero weight, the SSIM launch), the optimizer's baked constants (``betas``, ``eps``, ``weight_decay``) or ``clip_grad_norm`` change, the
-  graph is dropped and the next ``warmup`` calls run eagerly again before a new capture.  ``captures`` counts the captures.
+  config (the optional ``ssim_loss_weight`` / ``ssim_window`` / ``ssim_sigma`` / ``ssim_data_range`` and ``pixel_loss`` /
+  ``pixel_loss_param`` / ``contact_loss_weight`` / ``contact_threshold`` included: the captured loss is
+  ``functional.sr_loss_fwd_bwd``, the MSE or the configured pixel launch plus, for a non-zero weight, the SSIM launch),
+  the optimizer's baked constants (``betas``, ``eps``, ``weight_decay``) or ``clip_grad_norm`` change, the graph is dropped and the next ``warmup`` calls run eagerly again before a new capture.  ``captures`` counts the captures.
 * The returned ``total_loss`` is the graph's static OUTPUT BUFFER (like ``GraphedForward``): the next call overwrites
   it, so clone it to keep it.  It carries no autograd graph.
 * The captured step is one stream of launches: the train engine's forward and backward and the loss are driven
@@ -54,7 +55,7 @@ from .. import functional as Fh
 from .. import optim as opt_mod
 from .._lib import TactileSRHipError
 from ..ddp import note_forward
-from .tactileSR_train import _prep, ssim_loss_config, train_one_iter
+from .tactileSR_train import _prep, pixel_is_plain_mse, pixel_loss_config, ssim_loss_config, train_one_iter
 
 _CONFIG_KEYS = ("HR_scale_num", "scale_factor", "seqsCnt", "axisCnt")      # what the captured train_cal_loss bakes in
 
@@ -96,7 +97,8 @@ class GraphedTrainStep:
                        for g in opt.param_groups)
         return (m.train_impl, id(arena), arena.flat.data_ptr() if arena is not None else 0,
                 tuple(t.data_ptr() for t in m.parameters()), tuple(b.data_ptr() for b in m.buffers()), groups,
-                tuple(self.config[k] for k in _CONFIG_KEYS), ssim_loss_config(self.config), self.clip_grad_norm,
+                tuple(self.config[k] for k in _CONFIG_KEYS), ssim_loss_config(self.config), pixel_loss_config(self.config),
+                self.clip_grad_norm,
                 tuple(p.requires_grad for p in m.parameters()),      # the captured backward holds the trainable set's launches
                 tuple(mod.training for mod in m.modules() if isinstance(mod, torch.nn.BatchNorm2d)))      # and each BatchNorm's mode
 
@@ -128,6 +130,7 @@ class GraphedTrainStep:
     def _capture(self, LR, HR) -> None:
         m, opt = self.model, self.optimizer
         dev = next(m.parameters()).device
+        pixel = pixel_loss_config(self.config)     # refuses a bad key before anything is captured
         self._LR = torch.empty(LR.shape, dtype=LR.dtype, device=dev)
         self._HR = torch.empty(HR.shape, dtype=HR.dtype, device=dev)
         # one row of {lr, bc1, bc2_sqrt} per Adam launch; at most one launch per parameter
@@ -154,8 +157,11 @@ class GraphedTrainStep:
             if named:
                 note_forward(eng, ctx)
             weight, window, sigma, data_range = ssim_loss_config(self.config)
-            loss, dy, mse, vals = Fh.sr_loss_fwd_bwd(out.float(), HR, weight, data_range, window, sigma,
-                                                     return_parts=True)      # weight 0: mse_fwd_bwd alone
+            kind, param, fg_weight, fg_threshold = pixel
+            loss, dy, pix, vals = Fh.sr_loss_fwd_bwd(out.float(), HR, weight, data_range, window, sigma,
+                                                     return_parts=True, pixel_kind=kind, pixel_param=param,
+                                                     fg_weight=fg_weight, fg_threshold=fg_threshold)
+            # weight 0: the pixel launch alone; the plain MSE: mse_fwd_bwd
             ssim_mean = vals.mean() if vals is not None else None
             opt.zero_grad()
             grads = eng.backward(ctx, dy)
@@ -170,8 +176,11 @@ class GraphedTrainStep:
             launches = opt._captured_step(self._hyper, clip=self._norm[1:] if clip else None)
         # the launches (and the norm launch) hold the Adam chunk tables the graph reads: keep them alive with it
         out_dict = {"total_loss": loss[0]}
+        pix_key = "mse_loss" if pixel_is_plain_mse(pixel) else "pixel_loss"
         if vals is not None:                     # train_cal_loss's loss_dict with an SSIM term
-            out_dict.update(mse_loss=mse[0], ssim=ssim_mean)
+            out_dict.update({pix_key: pix[0], "ssim": ssim_mean})
+        elif pix_key == "pixel_loss":            # and with a configured pixel criterion alone
+            out_dict["pixel_loss"] = loss[0]
         self.graph, self._out, self._launches = graph, out_dict, launches
         self._norm_table = norm_table if clip else None
         self._graph_key = self._key()

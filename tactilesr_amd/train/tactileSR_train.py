@@ -38,16 +38,40 @@ def ssim_loss_config(config):
             float(config.get("ssim_sigma", 1.5)), float(config.get("ssim_data_range", 1.0)))
 
 
+def pixel_loss_config(config):
+    """The optional pixel-criterion keys ``(pixel_loss, pixel_loss_param, contact_loss_weight, contact_threshold)``,
+    defaults ``("mse", None, 0.0, 0.0)``: the criterion is ``mean_p w_p rho(out_p - HR_p)`` with ``rho`` the ``"mse"``
+    (the reference's nn.MSELoss, train/tactileSR_train.py:49), ``"l1"``, ``"charbonnier"`` (``pixel_loss_param`` = eps,
+    default 1e-3) or ``"huber"`` (delta, default 1.0) of ``functional.pixel_loss`` and
+    ``w_p = 1 + contact_loss_weight * [HR_p > contact_threshold]`` on the prepared target (after ``/HR_scale_num`` and
+    the resize).  Returned as the launch takes them, ``(name, param, weight, threshold)`` with the default parameter
+    filled in; an unknown name or a value the kernel would refuse raises ``TactileSRHipError`` here, before any launch."""
+    return Fh.pixel_loss_args(config.get("pixel_loss", "mse"), config.get("pixel_loss_param", None),
+                              config.get("contact_loss_weight", 0.0), config.get("contact_threshold", 0.0))
+
+
+def pixel_is_plain_mse(pixel) -> bool:
+    """Whether a ``pixel_loss_config`` result is the reference's criterion: the step then issues the MSE launch."""
+    return pixel[0] == "mse" and pixel[2] == 0
+
+
 def train_cal_loss(model, batch, config):
+    """``total_loss`` is always in the dict.  With an SSIM term it also holds ``ssim`` and the pixel term, under
+    ``mse_loss`` when that is the plain MSE; under any other pixel setting the term is reported as ``pixel_loss``."""
     device = next(model.parameters()).device
+    pixel = pixel_loss_config(config)
     LR, HR = _prep(batch, config, device)
     out = model(LR)
     weight, window, sigma, data_range = ssim_loss_config(config)
+    plain = pixel_is_plain_mse(pixel)
     if weight == 0:
-        loss = Fh.mse_loss(out, HR)
-        return loss, {"total_loss": loss}
-    loss, mse, vals = Fh.sr_loss(out, HR, weight, data_range, window, sigma)
-    return loss, {"total_loss": loss, "mse_loss": mse, "ssim": vals.mean()}
+        if plain:
+            loss = Fh.mse_loss(out, HR)
+            return loss, {"total_loss": loss}
+        loss = Fh.pixel_loss(out, HR, *pixel)
+        return loss, {"total_loss": loss, "pixel_loss": loss}
+    loss, pix, vals = Fh.sr_loss(out, HR, weight, data_range, window, sigma, *pixel)
+    return loss, {"total_loss": loss, "mse_loss" if plain else "pixel_loss": pix, "ssim": vals.mean()}
 
 
 def fused_clip_applies(model, optimizer) -> bool:

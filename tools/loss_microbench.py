@@ -12,7 +12,13 @@ Measures
 Every configuration of one comparison holds its own model from the same seed; all are warmed, then they alternate inside
 each of R rounds; reported are the median round and the spread (max - min) in ms, and for the steps the difference to
 weight 0 with the run's spread beside it.  Targets are contact-like blobs (the loss term is ~0 on white noise), the
-steps run at the reference's warm-up start learning rate, and a case whose output is all zero is marked invalid."""
+steps run at the reference's warm-up start learning rate, and a case whose output is all zero is marked invalid.
+
+    python tools/loss_microbench.py --pixel-loss [--rounds R] [--out profiles/pixel_loss_cost.json]
+times the pixel-loss launch (tsr_pixel_loss_fwd_bwd) instead, at B = 32 and B = 8192 of 1x40x40, in one process: the
+launch pair at every kind without and with a contact weight (and with the target gradient), the MSE launch pair
+(tsr_mse_fwd_bwd) beside it, both on preallocated buffers, and the same loss with its gradient composed from torch ops
+through autograd, the contact mask included.  Sparse contact targets, predictions relu(t + noise)."""
 import argparse
 import json
 import os
@@ -113,6 +119,74 @@ def kernel_cases(a):
     return cases
 
 
+PIXEL_BATCHES = (32, 8192)
+PIXEL_KINDS = (("mse", None), ("l1", None), ("charbonnier", 1e-3), ("huber", 1.0))
+CONTACT = (4.0, 0.5)            # weight, threshold
+
+
+def torch_pixel(y, t, kind, param, fg_weight, fg_threshold):
+    """The loss and d loss / d y from torch ops through autograd (the eager alternative)."""
+    yy = y.detach().requires_grad_(True)
+    d = yy - t
+    if kind == "mse":
+        rho = d * d
+    elif kind == "l1":
+        rho = d.abs()
+    elif kind == "charbonnier":
+        rho = torch.sqrt(d * d + param * param)
+    else:
+        a = d.abs()
+        rho = torch.where(a <= param, 0.5 * d * d, param * (a - 0.5 * param))
+    if fg_weight:
+        rho = rho * (1 + fg_weight * (t > fg_threshold))
+    loss = rho.mean()
+    return loss, torch.autograd.grad(loss, yy)[0]
+
+
+def pixel_cases(a):
+    from tactilesr_amd import _lib
+    from tactilesr_amd._lib import c_double, c_float, c_int, c_longlong, ptr, stream
+    cases = []
+    for B in PIXEL_BATCHES:
+        gen = torch.Generator().manual_seed(43)
+        shape = (B, 1, 40, 40)
+        t = torch.where(torch.rand(shape, generator=gen) < 0.1, 2 * torch.rand(shape, generator=gen), torch.zeros(shape)).cuda()
+        y = (t + 0.3 * torch.randn(shape, generator=gen).cuda()).clamp_min(0).contiguous()
+        n = y.numel()
+        dy, dt = torch.empty_like(y), torch.empty_like(y)
+        loss = torch.empty(1, device="cuda")
+        work = torch.empty(Fh.PIXEL_LOSS_WORK, dtype=torch.float64, device="cuda")
+
+        def pixel(kind, param, w, thr, with_dt=False):
+            _lib.call("tsr_pixel_loss_fwd_bwd", ptr(y), ptr(t), c_longlong(n), c_int(Fh.PIXEL_KINDS[kind]),
+                      c_double(param or 0.0), c_float(w), c_float(thr), ptr(loss), ptr(dy), c_float(1.0), c_int(0),
+                      ptr(dt if with_dt else None), ptr(work), stream())
+
+        fns = {"mse_fwd_bwd": lambda: _lib.call("tsr_mse_fwd_bwd", ptr(y), ptr(t), ptr(dy), ptr(loss), c_longlong(n),
+                                                c_float(1.0), ptr(work), stream())}
+        moved = {"mse_fwd_bwd": 3}                                  # tensors read or written: y, t, dy
+        for kind, param in PIXEL_KINDS:
+            fns[f"pixel_{kind}"] = lambda k=kind, p=param: pixel(k, p, 0.0, 0.0)
+            fns[f"pixel_{kind}_contact"] = lambda k=kind, p=param: pixel(k, p, *CONTACT)
+            fns[f"torch_{kind}"] = lambda k=kind, p=param: torch_pixel(y, t, k, p, 0.0, 0.0)
+            fns[f"torch_{kind}_contact"] = lambda k=kind, p=param: torch_pixel(y, t, k, p, *CONTACT)
+            moved[f"pixel_{kind}"] = moved[f"pixel_{kind}_contact"] = 3
+        fns["pixel_huber_contact_dt"] = lambda: pixel("huber", 1.0, *CONTACT, with_dt=True)
+        moved["pixel_huber_contact_dt"] = 4
+        rounds = alternate(fns, a.warmup, a.rounds, a.launches)
+        med = {k: statistics.median(v) for k, v in rounds.items()}
+        for k, v in rounds.items():
+            case = dict(shape=list(shape), launch=k, ms_median=round(med[k], 5), ms_spread=round(max(v) - min(v), 5),
+                        rounds_ms=[round(x, 5) for x in v], ratio_to_mse_fwd_bwd=round(med[k] / med["mse_fwd_bwd"], 3))
+            if k in moved:
+                case.update(bytes_moved=moved[k] * n * 4, gb_per_s=round(moved[k] * n * 4 / med[k] / 1e6, 1))
+            cases.append(case)
+            print(f"[loss microbench] pixel ({B},1,40,40) {k:26s}: {med[k]:8.4f} ms (spread {case['ms_spread']:.4f}), "
+                  f"{case['ratio_to_mse_fwd_bwd']:.2f} x mse_fwd_bwd" +
+                  (f", {case['gb_per_s']:.0f} GB/s" if k in moved else ""), flush=True)
+    return cases
+
+
 def build(weight):
     torch.manual_seed(42)
     m = tactilesr_amd.TactileSR().cuda().train()
@@ -187,16 +261,25 @@ def main():
     ap.add_argument("--only", choices=("kernel", "step"), default=None)
     ap.add_argument("--steps-of", choices=("b2048_eager", "b32_eager", "b32_graphed"), default=None,
                     help="time only this step comparison")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ssim_loss_cost.json"))
+    ap.add_argument("--pixel-loss", action="store_true", help="time the pixel-loss launch instead (see the docstring)")
+    ap.add_argument("--out", default=None, help="default: profiles/ssim_loss_cost.json, or profiles/pixel_loss_cost.json "
+                                                "with --pixel-loss")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "pixel_loss_cost.json" if a.pixel_loss else "ssim_loss_cost.json")
     if not torch.cuda.is_available():
         raise SystemExit("loss_microbench: needs a ROCm device (the timing is of the GPU)")
     result = dict(tool="tools/loss_microbench.py", device=torch.cuda.get_device_name(0), rounds=a.rounds, warmup=a.warmup,
                   launches=a.launches, steps=a.steps, weight=WEIGHT, lr=LR_START)
-    if a.only != "step":
-        result["kernel"] = kernel_cases(a)
-    if a.only != "kernel":
-        result["step"] = step_cases(a)
+    if a.pixel_loss:
+        result = dict(tool="tools/loss_microbench.py --pixel-loss", device=result["device"], rounds=a.rounds,
+                      warmup=a.warmup, launches=a.launches, contact_weight=CONTACT[0], contact_threshold=CONTACT[1],
+                      pixel=pixel_cases(a))
+    else:
+        if a.only != "step":
+            result["kernel"] = kernel_cases(a)
+        if a.only != "kernel":
+            result["step"] = step_cases(a)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(result, f, indent=1)
