@@ -589,6 +589,51 @@ int tsr_pixel_loss_fwd_bwd(const float* y, const float* t, long long n, int kind
                            float fg_threshold, float* loss, float* dy, float dy_scale, int accumulate, float* dt,
                            double* work, void* stream);
 
+/* Rot90 / flip augmentation on the device (csrc/dihedral.hip; the reference's augmentData, utility/raw_data_process.py:57-95,
+ * without storing four copies, plus the mirrored half of the dihedral group): gather sample idx[b] of src and write it
+ * transformed, in one pass and one launch.
+ *   out[b] = (accumulate ? out[b] : 0) + scale * D_{op[b]}( src[ idx ? idx[b] : b ] )        b < B
+ * src (n_src,C,H,W) and out (B,C,H,W) are fp32, contiguous, and must not overlap.  idx (B) is int64 on the device, NULL = the
+ * identity; op (B) is int32 on the device, one entry per output sample, NULL = the host argument op_all for every sample.
+ * Nothing is read back to the host: the launch can be captured in a HIP graph.  A data path: there is no backward entry.
+ * Op code: op = k + 4 f.  f = 1 mirrors along W first; then k counter-clockwise quarter turns are applied exactly as
+ * np.rot90(x, k, axes=(-2, -1)), so ops 0..3 are the reference's four.  Output element (i, j) is the source element
+ *   (a(u), b(v)), (u, v) = k odd ? (j, i) : (i, j), a(u) = [op & 2] ? H-1-u : u, b(v) = [popcount(op) odd] ? W-1-v : v.
+ * Arithmetic: scale == 1 with accumulate = 0 copies the 32-bit patterns (NaN payloads survive); otherwise an element is the
+ * one rounding of scale * x (accumulate = 0) or one fmaf(scale, x, out) (accumulate = 1).
+ * Channel map (optional): device arrays cmap[8][C] (int32 source channel) and csign[8][C] (float +1 or -1) indexed by op:
+ * output plane c is D_op of source plane cmap[op][c], times csign[op][c] before scale.  The sign is applied by flipping the
+ * sign bit when csign is negative -- the exact product for +-1, and a NaN keeps its payload; the magnitude is not read.
+ * Both NULL: every plane is transformed on its own (the reference).  This carries the "vector" axis mode of
+ * functional.dihedral_axis_tables.
+ * Safety: a bad device value never becomes an out-of-range access.  op_mask is a host bitmask (bit o = op o may occur).  A
+ * sample whose op[b] is outside 0..7 or not in op_mask, whose source index (idx[b], or b itself without idx) is outside
+ * [0, n_src), or a plane whose cmap entry is outside [0, C), is written as all-NaN (whatever accumulate says); no other
+ * sample is touched.
+ * Kernels: planes of at most 64 elements go one thread per output element; planes with H (W + 1) <= 15872 (62 KiB of LDS:
+ * up to 125x125, every shape of the project) go one workgroup a plane, larger ones as 64x64 tiles, one workgroup a tile;
+ * the op is uniform per workgroup.  Even k reverses rows / columns in registers; odd k (a transpose) stages the plane or
+ * tile through LDS (row pitch W + 1, 65) so that the global reads and writes both run along rows; float4 accesses where
+ * src and out are 16-byte aligned and W % 4 == 0, one float per lane otherwise.  No atomics: two launches give the same
+ * bits.
+ * Index arithmetic: offsets inside a sample are 32-bit, so C*H*W <= 2^31 - 1; sample offsets (B*C*H*W, n_src*C*H*W) are
+ * 64-bit and cannot overflow under that bound; the grid is capped and walked, so B is not bounded by the launch.
+ * Refusals (status 1, before any device call, nothing written): a NULL src or out; B, n_src, C, H or W <= 0; op_mask 0,
+ * negative or with bits above 7; an odd-k bit in op_mask while H != W; op NULL with op_all outside 0..7 or not in op_mask;
+ * exactly one of cmap / csign; C*H*W > 2^31 - 1; accumulate not 0 or 1; scale NaN. */
+int tsr_gather_dihedral(const float* src, int n_src, const long long* idx, const int* op, int op_all, int op_mask,
+                        const int* cmap, const float* csign, float* out, int B, int C, int H, int W, float scale,
+                        int accumulate, void* stream);
+/* The same launch with the caller's grid cap: at most max_wgs workgroups are launched, and a workgroup walks the
+ * further work items (elements, planes or tiles) at a stride of the grid -- a caller that shares the device with
+ * another stream can leave it CUs, and the walk of every kernel can be run at any size.  The result does not depend
+ * on max_wgs, bit for bit.  tsr_gather_dihedral is this with max_wgs = TSR_DIHEDRAL_MAX_WGS.  Refusals: those of
+ * tsr_gather_dihedral, and max_wgs <= 0. */
+#define TSR_DIHEDRAL_MAX_WGS (1 << 20)
+int tsr_gather_dihedral_wgs(const float* src, int n_src, const long long* idx, const int* op, int op_all, int op_mask,
+                            const int* cmap, const float* csign, float* out, int B, int C, int H, int W, float scale,
+                            int accumulate, int max_wgs, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * tPSFNet (model/tPSFNet.py): batched, one workgroup per sample (the reference loops over the
  * batch in python, :118-125).  size is fixed at 100x100 depth / 99x99 PSF / 4x4 taxels, as the

@@ -96,6 +96,8 @@ SIGNATURES = {
     "tsr_psnr_ssim": [_P, _P, _I, _I, c_double, c_double, c_double, c_double, _P, _P, _P],
     "tsr_ssim_fwd_bwd": [_P, _P, _I, _I, _I, _I, c_double, c_double, c_double, _P, _P, _F, _I, _P],
     "tsr_pixel_loss_fwd_bwd": [_P, _P, _L, _I, c_double, _F, _F, _P, _P, _F, _I, _P, _P, _P],
+    "tsr_gather_dihedral": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
+    "tsr_gather_dihedral_wgs": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
     "tpsf_forward": [_P, _P, _P, _P, _P, _I, _P],
     "tpsf_backward": [_P, _P, _P, _P, _P, _P, _I, _P],
     "tpsf_backward_ex": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],

@@ -18,10 +18,48 @@ import torch
 
 
 class DeviceSRLoader:
+    """``augment`` (default ``None``: the plain loader, untouched) switches on rot90 / flip augmentation on the device:
+    ``"rot90"`` (ops 0..3, the reference's ``augmentData``, utility/raw_data_process.py:57-95), ``"dihedral"`` (ops 0..7)
+    or an explicit tuple of ops ``k + 4 f`` (``functional.dihedral``).  Each batch is one ``tsr_gather_dihedral`` launch
+    per tensor -- the gather and the transform in one pass -- and both tensors of a pair get the same op.
+
+    * ``augment_mode="random"``: each epoch, after the permutation, one op per sample is drawn uniformly from the set
+      with the loader's own generator; the epoch's length is unchanged.
+    * ``augment_mode="expand"``: the epoch covers every (sample, op) pair once; virtual index ``j`` is sample
+      ``j // n_ops`` under ``ops[j % n_ops]`` -- unshuffled, ``augmentData``'s order without storing the copies -- and
+      ``len()`` grows by the factor ``n_ops``.
+
+    ``axis_mode="vector"`` also maps the in-plane force channels of the first tensor
+    (``functional.dihedral_axis_tables``); the second tensor, ``(N,H,W)`` or ``(N,C,H,W)``, is always turned plane by
+    plane.  ``last_index`` / ``last_ops`` hold the latest augmented batch's device arrays (int64 / int32).  Rank
+    sharding stays on the base samples.  The batches carry no autograd graph."""
+
     def __init__(self, LR: torch.Tensor, HR: torch.Tensor, batch_size: int, shuffle: bool = False,
                  drop_last: bool = False, seed: Optional[int] = None, device="cuda",
-                 rank: int = 0, world_size: int = 1):
+                 rank: int = 0, world_size: int = 1, augment=None, augment_mode: str = "random",
+                 axis_mode: str = "planes", axis_cnt: int = 3):
         assert LR.shape[0] == HR.shape[0], "LR and HR must hold the same number of samples"
+        self._ops = None
+        self.last_index = self.last_ops = None
+        if augment is not None:
+            from .. import functional as Fh
+            from .._lib import TactileSRHipError
+            self._ops = Fh.dihedral_ops(augment)
+            if augment_mode not in ("random", "expand"):
+                raise TactileSRHipError(f"augment_mode {augment_mode!r} is not 'random' or 'expand'")
+            if axis_mode not in Fh.AXIS_MODES:
+                raise TactileSRHipError(f"axis_mode {axis_mode!r} is not one of {Fh.AXIS_MODES}")
+            if LR.dim() != 4 or HR.dim() not in (3, 4):
+                raise TactileSRHipError("augmentation needs a (N,C,H,W) first tensor and a (N,H,W) or (N,C,H,W) second one, "
+                                        f"got {tuple(LR.shape)} and {tuple(HR.shape)}")
+            if any(o & 1 for o in self._ops):
+                for name, t in (("first", LR), ("second", HR)):
+                    if t.shape[-1] != t.shape[-2]:
+                        raise TactileSRHipError(f"a quarter turn (odd k) needs square planes; the {name} tensor is "
+                                                f"{tuple(t.shape)}")
+            self.augment_mode, self.axis_mode = augment_mode, axis_mode
+            self._op_mask = Fh.dihedral_op_mask(self._ops)
+            self._tables = Fh.dihedral_axis_tables(LR.shape[1], axis_cnt) if axis_mode == "vector" else None
         dev = torch.device(device)
         # shard of the set for this rank (data-parallel training: one process per GPU).  EVERY rank gets the same
         # number of samples -- ceil(n/world), the tail wrapping around to the head like DistributedSampler's padding --
@@ -37,6 +75,10 @@ class DeviceSRLoader:
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(0 if seed is None else int(seed))
         self.epoch = 0
+        if self._ops is not None:
+            self._ops_t = torch.tensor(self._ops, dtype=torch.int32, device=dev)
+            if self._tables is not None:
+                self._tables = tuple(t.to(dev) for t in self._tables)
 
     @classmethod
     def from_entries(cls, entries: List[list], batch_size: int, **kw) -> "DeviceSRLoader":
@@ -54,10 +96,34 @@ class DeviceSRLoader:
         return cls.from_entries(entries, batch_size, **kw)
 
     def __len__(self) -> int:
-        n = self.LR.shape[0]
+        n = self._virtual_len()
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
+    def _virtual_len(self) -> int:
+        n = self.LR.shape[0]
+        return n * len(self._ops) if self._ops is not None and self.augment_mode == "expand" else n
+
+    def _iter_augmented(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        from .. import functional as Fh
+        dev, n, n_ops = self.LR.device, self._virtual_len(), len(self._ops)
+        order = torch.randperm(n, generator=self._gen, device=dev) if self.shuffle else torch.arange(n, device=dev)
+        if self.augment_mode == "expand":
+            index, ops = torch.div(order, n_ops, rounding_mode="floor"), self._ops_t[order % n_ops]
+        else:
+            index = order
+            ops = self._ops_t[torch.randint(0, n_ops, (n,), generator=self._gen, device=dev)]
+        self.epoch += 1
+        for i in range(len(self)):
+            lo, hi = i * self.batch_size, min(n, (i + 1) * self.batch_size)
+            idx, op = index[lo:hi].contiguous(), ops[lo:hi].contiguous()
+            self.last_index, self.last_ops = idx, op
+            yield (Fh.dihedral(self.LR, op, idx, axis_mode=self.axis_mode, op_mask=self._op_mask, tables=self._tables),
+                   Fh.dihedral(self.HR, op, idx, op_mask=self._op_mask))
+
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        if self._ops is not None:
+            yield from self._iter_augmented()
+            return
         n = self.LR.shape[0]
         order = torch.randperm(n, generator=self._gen, device=self.LR.device) if self.shuffle else None
         self.epoch += 1

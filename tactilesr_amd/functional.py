@@ -251,3 +251,229 @@ def psnr_ssim(a: torch.Tensor, b: torch.Tensor, maxValue: float, reference_quirk
     ss = torch.empty(B, dtype=torch.float32, device=a.device)
     call("tsr_psnr_ssim", ptr(a), ptr(b), _I(B), _I(n), _D(div), _D(maxValue), _D(C1), _D(C2), ptr(ps), ptr(ss), stream())
     return ps, ss
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Rot90 / flip augmentation and the geometric self-ensemble (tsr_gather_dihedral, csrc/dihedral.hip).  A data path: none
+# of it is differentiable, and nothing here builds an autograd graph.
+# ----------------------------------------------------------------------------------------------------------------------
+DIHEDRAL_SETS = {"rot90": (0, 1, 2, 3), "dihedral": (0, 1, 2, 3, 4, 5, 6, 7)}
+AXIS_MODES = ("planes", "vector")
+
+
+def _dihedral_parts(op: int):
+    """``(transpose, flip source rows, flip source columns)`` of op = k + 4 f: output (i, j) is the source element
+    ``(a(u), b(v))`` with ``(u, v) = (j, i)`` under a transpose."""
+    return bool(op & 1), bool(op & 2), bool(bin(op).count("1") & 1)
+
+
+def _dihedral_coord(op: int, i: int, j: int, n: int):
+    tr, fr, fc = _dihedral_parts(op)
+    u, v = (j, i) if tr else (i, j)
+    return (n - 1 - u if fr else u), (n - 1 - v if fc else v)
+
+
+def _dihedral_tables():
+    n = 3
+    maps = [tuple(_dihedral_coord(op, i, j, n) for i in range(n) for j in range(n)) for op in range(8)]
+    comp = [[0] * 8 for _ in range(8)]
+    for a in range(8):
+        for b in range(8):
+            # D_b(D_a(x)): element (i, j) of the result is element D_b-coordinate of D_a(x), itself a D_a-coordinate of x
+            both = tuple(_dihedral_coord(a, *_dihedral_coord(b, i, j, n), n) for i in range(n) for j in range(n))
+            comp[a][b] = maps.index(both)
+    inv = [comp[a].index(0) for a in range(8)]
+    return comp, inv
+
+
+_DIHEDRAL_COMPOSE, _DIHEDRAL_INVERSE = _dihedral_tables()
+
+
+def _check_op(op) -> int:
+    o = int(op)
+    if o != op or not 0 <= o <= 7:
+        raise TactileSRHipError(f"a dihedral op is an integer in 0..7 (k + 4 f), got {op!r}")
+    return o
+
+
+def dihedral_compose(a: int, b: int) -> int:
+    """The op c with ``D_c(x) = D_b(D_a(x))``: ``a`` first, then ``b``.  Host-only integer table."""
+    return _DIHEDRAL_COMPOSE[_check_op(a)][_check_op(b)]
+
+
+def dihedral_inverse(op: int) -> int:
+    """The op that undoes ``op``: ``dihedral_compose(op, dihedral_inverse(op)) == 0``.  Host-only integer table."""
+    return _DIHEDRAL_INVERSE[_check_op(op)]
+
+
+def dihedral_ops(spec) -> tuple:
+    """``"rot90"`` -> ops 0..3 (the reference's augmentData), ``"dihedral"`` -> ops 0..7, or an explicit non-empty
+    sequence of distinct ops, as a tuple."""
+    if isinstance(spec, str):
+        if spec not in DIHEDRAL_SETS:
+            raise TactileSRHipError(f"op set {spec!r} is not one of {sorted(DIHEDRAL_SETS)} or a tuple of ops")
+        return DIHEDRAL_SETS[spec]
+    try:
+        ops = tuple(_check_op(o) for o in spec)
+    except TypeError:
+        raise TactileSRHipError(f"op set {spec!r} is not one of {sorted(DIHEDRAL_SETS)} or a tuple of ops") from None
+    if not ops or len(set(ops)) != len(ops):
+        raise TactileSRHipError(f"an op set needs at least one op and no repeats, got {ops}")
+    return ops
+
+
+def dihedral_op_mask(ops) -> int:
+    m = 0
+    for o in ops:
+        m |= 1 << _check_op(o)
+    return m
+
+
+def dihedral_axis_tables(C: int, axis_cnt: int = 3):
+    """``(cmap (8, C) int32, csign (8, C) float32)`` of ``axis_mode="vector"``, CPU tensors.  Within each group of
+    ``axis_cnt`` channels, channel 0 is the force along +H (rows), channel 1 the force along +W and channel 2 (and any
+    further one) a scalar such as the normal force (the layout sketched in utility/raw_data_process.py:134-141).  The
+    pair (0, 1) transforms with the op's 2x2 coordinate matrix -- a mirror or a turn also turns the in-plane force --
+    and the other channels never change.  Output plane c is ``csign[op][c] * D_op(plane cmap[op][c])``."""
+    C, axis_cnt = int(C), int(axis_cnt)
+    if axis_cnt < 2 or C <= 0 or C % axis_cnt:
+        raise TactileSRHipError(f"vector axis mode needs C a positive multiple of axis_cnt >= 2, got C={C}, axis_cnt={axis_cnt}")
+    cmap = torch.arange(C, dtype=torch.int32).repeat(8, 1)
+    csign = torch.ones(8, C, dtype=torch.float32)
+    for op in range(8):
+        tr, fr, fc = _dihedral_parts(op)
+        sr, sc = (-1.0 if fr else 1.0), (-1.0 if fc else 1.0)
+        for g in range(0, C, axis_cnt):
+            # source (r, c) lands at i = sr r, j = sc c, or under a transpose at i = sc c, j = sr r
+            cmap[op, g], cmap[op, g + 1] = (g + 1, g) if tr else (g, g + 1)
+            csign[op, g], csign[op, g + 1] = (sc, sr) if tr else (sr, sc)
+    return cmap, csign
+
+
+def _dihedral_plane_torch(x: torch.Tensor, op: int) -> torch.Tensor:
+    if op & 4:
+        x = x.flip(-1)
+    return torch.rot90(x, op & 3, (-2, -1))
+
+
+def _dihedral_torch(x, ops, index, out, scale, accumulate, tables, op_all):
+    """The transform composed from torch ops (index_select, flip, rot90): CPU tensors and dtypes other than fp32."""
+    n_out = x.shape[0] if index is None else int(index.shape[0])
+    src = x if index is None else x.index_select(0, index.to(x.device).long())
+    op_list = [int(op_all)] * n_out if ops is None else [int(o) for o in torch.as_tensor(ops).tolist()]
+    if len(op_list) != n_out:
+        raise TactileSRHipError(f"dihedral: {len(op_list)} ops for {n_out} output samples")
+    res = torch.empty_like(src)
+    for op in sorted(set(op_list)):
+        _check_op(op)
+        sel = torch.tensor([k for k, o in enumerate(op_list) if o == op], dtype=torch.long, device=x.device)
+        part = src.index_select(0, sel)
+        if tables is not None:
+            cmap, csign = tables
+            part = part.index_select(1, cmap[op].to(x.device).long())
+            neg = (csign[op] < 0).to(x.device).view(1, -1, 1, 1)
+            part = torch.where(neg, -part, part)
+        res.index_copy_(0, sel, _dihedral_plane_torch(part, op))
+    if scale == 1.0 and not accumulate:
+        val = res
+    elif not accumulate:
+        val = res * scale
+    else:
+        val = (out.double() + float(scale) * res.double()).to(res.dtype)
+    if out is None:
+        return val.contiguous()
+    out.copy_(val)
+    return out
+
+
+def _memory_overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """Whether two tensors of one device touch a common byte: the byte ranges of contiguous tensors, else (a strided
+    view) whether they share a storage."""
+    if a.device != b.device or a.numel() == 0 or b.numel() == 0:
+        return False
+    if a.is_contiguous() and b.is_contiguous():
+        a0, b0 = a.data_ptr(), b.data_ptr()
+        return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+    return a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+
+
+def dihedral(x: torch.Tensor, ops=None, index=None, out=None, scale: float = 1.0, accumulate: bool = False,
+             axis_mode: str = "planes", op_all: int = 0, *, op_mask=None, axis_cnt: int = 3, tables=None) -> torch.Tensor:
+    """``out[b] = (accumulate ? out[b] : 0) + scale * D_{ops[b]}(x[index[b]])``: gather and rot90 / flip in one
+    ``tsr_gather_dihedral`` launch.  ``x`` is ``(N, C, H, W)`` or ``(N, H, W)``; ``ops`` an int32 tensor (or a sequence)
+    of one op per output sample, ``None`` = ``op_all`` for all; ``index`` an int64 tensor (or a sequence), ``None`` = the
+    identity; ``out``, when given, must not overlap ``x`` in memory (the kernel reads while it writes).  An
+    op is ``k + 4 f``: mirror along W when ``f``, then ``np.rot90(x, k, axes=(-2, -1))``.  ``axis_mode="planes"``
+    transforms every plane on its own (the reference); ``"vector"`` also maps the in-plane force channels
+    (``dihedral_axis_tables(C, axis_cnt)``).  Keyword-only, beyond the reference-shaped arguments: ``tables`` passes device
+    copies of those tables made once (the loader does), ``axis_cnt`` their group size, and ``op_mask`` (default: every op
+    the shape admits, or ``op_all`` alone) is the set of ops the launch accepts: a sample with any other op, or with an
+    index outside ``x``, comes out all-NaN, never as an out-of-range access.  No host synchronisation on a ROCm fp32
+    tensor.  A CPU tensor or another dtype takes a torch-composed path with the same results (it reads ``ops`` on the
+    host and raises on a bad op).  Not differentiable: a data path, run it outside autograd."""
+    if axis_mode not in AXIS_MODES:
+        raise TactileSRHipError(f"axis_mode {axis_mode!r} is not one of {AXIS_MODES}")
+    if x.dim() == 3:
+        res = dihedral(x.unsqueeze(1), ops, index, None if out is None else out.unsqueeze(1), scale, accumulate,
+                       axis_mode, op_all, op_mask=op_mask, axis_cnt=axis_cnt, tables=tables)
+        return res.squeeze(1)
+    if x.dim() != 4:
+        raise TactileSRHipError(f"dihedral needs (N,C,H,W) or (N,H,W), got {tuple(x.shape)}")
+    x = x.detach()
+    n_src, C, H, W = x.shape
+    if index is not None:
+        index = torch.as_tensor(index, device=x.device).to(torch.int64).contiguous()
+        if index.dim() != 1:
+            raise TactileSRHipError(f"dihedral: index must be one-dimensional, got {tuple(index.shape)}")
+    B = n_src if index is None else int(index.shape[0])
+    if accumulate and out is None:
+        raise TactileSRHipError("dihedral: accumulate=True needs the out to add to")
+    if out is not None and (tuple(out.shape) != (B, C, H, W) or out.dtype != x.dtype or out.device != x.device):
+        raise TactileSRHipError("dihedral: out must have shape (B,C,H,W), and x's dtype and device")
+    if out is not None and _memory_overlaps(x, out):
+        raise TactileSRHipError("dihedral: out overlaps x in memory; the transform is not done in place")
+    if axis_mode == "vector" and tables is None:
+        tables = tuple(t.to(x.device) for t in dihedral_axis_tables(C, axis_cnt))
+    elif axis_mode == "planes":
+        tables = None
+    if not x.is_cuda or x.dtype != torch.float32:
+        return _dihedral_torch(x, ops, index, out, float(scale), bool(accumulate), tables, op_all)
+    x = x.contiguous()
+    if ops is not None:
+        ops = torch.as_tensor(ops, device=x.device).to(torch.int32).contiguous()
+        if ops.shape != (B,):
+            raise TactileSRHipError(f"dihedral: ops must hold one op per output sample ({B}), got {tuple(ops.shape)}")
+    if op_mask is None:
+        op_mask = (1 << _check_op(op_all)) if ops is None else (0xff if H == W else 0x55)
+    if out is None:
+        out = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
+    elif not out.is_contiguous():
+        raise TactileSRHipError("dihedral: out must be contiguous")
+    cmap, csign = tables if tables is not None else (None, None)
+    call("tsr_gather_dihedral", ptr(x), _I(n_src), ptr(index), ptr(ops), _I(int(op_all)), _I(int(op_mask)), ptr(cmap),
+         ptr(csign), ptr(out), _I(B), _I(C), _I(H), _I(W), _F(float(scale)), _I(1 if accumulate else 0), stream())
+    return out
+
+
+@torch.no_grad()
+def self_ensemble(model, LR: torch.Tensor, ops="dihedral", axis_mode: str = "planes") -> torch.Tensor:
+    """Geometric self-ensemble: the mean over ``ops`` of ``D_op^-1(model(D_op(LR)))``, in eval mode and under
+    ``no_grad`` (the model's training flag is restored).  For each op the whole batch is transformed with ``op_all``,
+    the model runs, and ``(1/n) D_op^-1(y)`` is accumulated by the kernel's ``accumulate`` form: one rounding of the
+    first term (none when 1/n is a power of two) and one fma per further term.  ``ops``: ``"dihedral"`` (8),
+    ``"rot90"`` (4) or a tuple; ``ops=(0,)`` is ``model(LR)`` bit for bit.  ``axis_mode`` applies to ``LR``; the
+    output is an image and is turned back plane by plane.  Not differentiable."""
+    ops = dihedral_ops(ops)
+    was_training = model.training
+    model.eval()
+    try:
+        acc, w = None, 1.0 / len(ops)
+        for op in ops:
+            y = model(dihedral(LR, op_all=op, axis_mode=axis_mode))
+            if acc is None:
+                acc = dihedral(y, op_all=dihedral_inverse(op), scale=w)
+            else:
+                dihedral(y, op_all=dihedral_inverse(op), out=acc, scale=w, accumulate=True)
+    finally:
+        model.train(was_training)
+    return acc

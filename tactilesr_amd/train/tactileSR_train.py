@@ -128,10 +128,14 @@ def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite
 
 
 @torch.no_grad()
-def eval_func(model, test_loader, config, windowed_ssim=False):
+def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=None):
     """The reference's three averages (loss, SSIM, PSNR).  ``windowed_ssim=True`` appends a fourth: the windowed SSIM
     of ``functional.ssim`` with the config's ``ssim_window`` / ``ssim_sigma`` / ``ssim_data_range`` (``ssim_loss_config``),
-    averaged the same way; the first three are unchanged."""
+    averaged the same way; the first three are unchanged.
+
+    ``self_ensemble`` (``None``, the default: one forward per batch, the results unchanged) names an op set of
+    ``functional.self_ensemble`` -- ``"dihedral"``, ``"rot90"`` or a tuple of ops -- and scores the mean of the model's
+    outputs over those transforms of the taxels (plane by plane) instead."""
     device = next(model.parameters()).device
     model.eval()
     tot_loss = tot_ssim = tot_psnr = tot_wssim = 0.0
@@ -139,7 +143,7 @@ def eval_func(model, test_loader, config, windowed_ssim=False):
     _, window, sigma, data_range = ssim_loss_config(config)
     for batch in test_loader:
         LR, HR = _prep(batch, config, device)
-        out = model(LR)
+        out = model(LR) if self_ensemble is None else Fh.self_ensemble(model, LR.contiguous(), self_ensemble)
         tot_loss += float(Fh.mse_loss(out, HR))
         ps, ss = Fh.psnr_ssim(out, HR, config["sensorMaxVaule_factor"], reference_quirk=True)
         tot_psnr += float(ps.mean())
