@@ -521,6 +521,32 @@ int tsr_adam_l2_multi_clip(const tsr_adam_chunk* chunks, int n_chunks, float lr,
 int tsr_adam_l2_multi_dev_clip(const tsr_adam_chunk* chunks, int n_chunks, const float* hyper, double beta1,
                                double beta2, float eps, float weight_decay, const float* clip, void* stream);
 
+/* Weight averaging (EMA / SWA) of every tensor of a state dict in ONE launch.  `chunks` is a DEVICE array of n_chunks
+ * records, one per piece of 1..4096 4-byte words of a tensor, pointers already offset to the piece: avg is the average
+ * (the shadow), src the live tensor.  One workgroup of 256 threads per record; 16-byte accesses when both pointers of
+ * the record are 16-byte aligned, scalar otherwise (and for the tail).  mode 0 = fp32 values, mode 1 = raw words
+ * (integer buffers such as num_batches_tracked, an int64 as two words per element, or a buffer to be copied).
+ *   op 0 UPDATE  mode 0: avg = fmaf(omd, src - avg, avg), omd = one_minus_decay, the subtraction rounded in fp32
+ *                        (|result - exact| <= 3 * 2^-24 * max(|src|, |avg|));  mode 1: avg = src.
+ *   op 1 STORE   avg = src for every record (initialisation)
+ *   op 2 LOAD    src = avg for every record
+ *   op 3 SWAP    the two are exchanged for every record
+ * STORE, LOAD, SWAP and mode 1 move raw words: bit for bit, NaN payloads and integers included; two SWAPs are the
+ * identity on bits.  UPDATE consequences: src == avg (the same value, or a record naming the same words twice: a frozen
+ * parameter) leaves a finite avg unchanged bit for bit (src - avg is +0; a -0 average becomes the equal +0, an Inf one
+ * NaN, as Inf - Inf is); avg == 0 with omd == 1 gives src exactly; a NaN or Inf stays in its own element.  avg and src
+ * of one record may be identical but must not overlap otherwise, and no two records may share a word.
+ * tsr_ema_multi_dev reads omd from the DEVICE float one_minus_decay_dev instead of a kernel argument, so a captured
+ * graph replays the launch with the value written before that replay (a decay that warms up); same kernel body, same
+ * bits for the same float.  Its value is the caller's to keep in [0, 1].
+ * Refused with TSR_ERR_ARG before any launch: chunks NULL, n_chunks <= 0, op outside 0..3, one_minus_decay NaN or
+ * outside [0, 1], one_minus_decay_dev NULL.  A record whose n is outside 1..4096 or whose mode is outside 0..1 is
+ * skipped by its workgroup: nothing is read or written through its pointers. */
+typedef struct tsr_ema_chunk { float* avg; float* src; int n; int mode; } tsr_ema_chunk;
+int tsr_ema_multi(const tsr_ema_chunk* chunks, int n_chunks, int op, float one_minus_decay, void* stream);
+int tsr_ema_multi_dev(const tsr_ema_chunk* chunks, int n_chunks, int op, const float* one_minus_decay_dev,
+                      void* stream);
+
 /* Per-sample PSNR / SSIM of eval_func (train/tactileSR_train.py:87-94, utility/tools.py:49-81) for B samples
  * of n elements: PSNR = 10log10(max^2/(sum(a-b)^2/psnr_div)) with psnr_div = shape[0]*shape[1] of what the
  * reference passes ((1,H,W) -> H, its /40 quirk; (H,W) -> H*W); SSIM = one global window. */

@@ -7,5 +7,6 @@ HIP kernel in ``lib/libtactilesr_hip.so`` reached through the C ABI of
 from . import _lib  # noqa: F401
 from .model.tactileSR_model import TactileSR, TactileSRCNN, MSRB, ResBlock  # noqa: F401
 from .model.tPSFNet import tPSFNet  # noqa: F401
+from .ema import WeightEMA, recalibrate_bn  # noqa: F401
 
-__all__ = ["TactileSR", "TactileSRCNN", "MSRB", "ResBlock", "tPSFNet"]
+__all__ = ["TactileSR", "TactileSRCNN", "MSRB", "ResBlock", "tPSFNet", "WeightEMA", "recalibrate_bn"]

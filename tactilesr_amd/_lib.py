@@ -93,6 +93,8 @@ SIGNATURES = {
     "tsr_grad_norm_multi": [_P, _I, _F, _P, _P, _P],
     "tsr_adam_l2_multi_clip": [_P, _I, _F, c_double, c_double, _F, _F, _I, _P, _P],
     "tsr_adam_l2_multi_dev_clip": [_P, _I, _P, c_double, c_double, _F, _F, _P, _P],
+    "tsr_ema_multi": [_P, _I, _I, _F, _P],
+    "tsr_ema_multi_dev": [_P, _I, _I, _P, _P],
     "tsr_psnr_ssim": [_P, _P, _I, _I, c_double, c_double, c_double, c_double, _P, _P, _P],
     "tsr_ssim_fwd_bwd": [_P, _P, _I, _I, _I, _I, c_double, c_double, c_double, _P, _P, _F, _I, _P],
     "tsr_pixel_loss_fwd_bwd": [_P, _P, _L, _I, c_double, _F, _F, _P, _P, _F, _I, _P, _P, _P],

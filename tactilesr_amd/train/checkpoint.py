@@ -19,12 +19,14 @@ import torch
 
 def save_checkpoint(path: str, model, optimizer=None, lr_scheduler=None, epoch: Optional[int] = None,
                     iteration: Optional[int] = None, num_gpus: Optional[int] = None, metric_storage=None,
-                    hooks: Optional[dict] = None, grad_scaler=None, reference_layout: bool = False) -> None:
+                    hooks: Optional[dict] = None, grad_scaler=None, reference_layout: bool = False, ema=None) -> None:
     """Write the dict of reference cpu/trainer.py:401-411.  ``metric_storage`` defaults to an empty
     ``tactilesr_amd.train.metrics.MetricStorage`` -- the reference installs whatever object sits under that key as its
     live store on resume (cpu/trainer.py:469), so ``None`` would break it.  ``grad_scaler`` (a GradScaler or its state
     dict) is written only when given: the reference asserts that the key is present iff AMP is on (:477-478).
-    ``reference_layout=True`` writes the LR-scheduler state in the key layout of the reference's warm-up class."""
+    ``reference_layout=True`` writes the LR-scheduler state in the key layout of the reference's warm-up class.
+    ``ema`` (a ``tactilesr_amd.WeightEMA``) adds an ``ema`` entry, its ``state_dict()`` -- tensors and plain scalars only;
+    without one the key is not written and the file has the layout above."""
     module = model.module if hasattr(model, "module") else model     # DDP unwrap (cpu/trainer.py:172-176)
     if num_gpus is None:
         num_gpus = torch.distributed.get_world_size() if (torch.distributed.is_available()
@@ -44,6 +46,8 @@ def save_checkpoint(path: str, model, optimizer=None, lr_scheduler=None, epoch: 
         data["hooks"] = hooks
     if grad_scaler is not None:
         data["grad_scaler"] = grad_scaler.state_dict() if hasattr(grad_scaler, "state_dict") else grad_scaler
+    if ema is not None:
+        data["ema"] = ema.state_dict()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     torch.save(data, path)
     latest = os.path.join(os.path.dirname(os.path.abspath(path)), "latest.pth")
@@ -54,7 +58,7 @@ def save_checkpoint(path: str, model, optimizer=None, lr_scheduler=None, epoch: 
 
 def load_checkpoint(path: str, model, optimizer=None, lr_scheduler=None, num_gpus: Optional[int] = None,
                     trusted: bool = False, grad_scaler=None, hooks: Optional[dict] = None,
-                    epoch_len: Optional[int] = None) -> dict:
+                    epoch_len: Optional[int] = None, ema=None) -> dict:
     """Restore model (strict=False like the reference), optimizer, scheduler, grad scaler and hook states, in the
     order of reference cpu/trainer.py:440-498; returns the checkpoint dict with ``start_iter`` added
     (``(epoch+1)*epoch_len`` or ``iter+1``, :452-457).
@@ -62,6 +66,8 @@ def load_checkpoint(path: str, model, optimizer=None, lr_scheduler=None, num_gpu
     ``hooks``: {class name: object with load_state_dict}; states without a taker and takers without a state are
     reported in ``ck['hooks_missing']`` / ``ck['hooks_unexpected']`` (the reference only warns).  AMP consistency
     (:477-478): a ``grad_scaler`` argument demands a ``grad_scaler`` entry and vice versa.
+    ``ema`` (a ``tactilesr_amd.WeightEMA`` of ``model``) is restored after the model from the file's ``ema`` entry; a file
+    without one restarts the average from the loaded weights (``ema.reset()``) and sets ``ck['ema_missing'] = True``.
     Files written by this package load with the restricted unpickler (``weights_only=True`` + this package's metric
     store classes allow-listed); a file that carries other pickled python objects (every reference-written file does:
     its MetricStorage instance) needs ``trusted=True`` -- only for files whose origin you trust."""
@@ -83,6 +89,12 @@ def load_checkpoint(path: str, model, optimizer=None, lr_scheduler=None, num_gpu
     module = model.module if hasattr(model, "module") else model
     incompatible = module.load_state_dict(ck["model"], strict=False)
     ck["missing_keys"], ck["unexpected_keys"] = list(incompatible.missing_keys), list(incompatible.unexpected_keys)
+    if ema is not None:
+        if ck.get("ema") is not None:
+            ema.load_state_dict(ck["ema"])
+        else:
+            ema.reset()
+            ck["ema_missing"] = True
     if optimizer is not None and ck.get("optimizer") is not None:
         optimizer.load_state_dict(ck["optimizer"])
     if lr_scheduler is not None and ck.get("lr_scheduler") is not None:

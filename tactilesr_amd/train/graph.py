@@ -41,10 +41,17 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
   model parameter is stepped by the optimizer (refused otherwise, e.g. the Seqs transplant, whose new parameters are
   not in the optimizer; ``model_param_init(..., freeze=True)`` freezes them and the flow is accepted).  ``c <= 0`` (the
   default) captures the step as before.
+* Weight averaging: ``GraphedTrainStep(..., ema=e)`` with a ``tactilesr_amd.WeightEMA`` is ``train_one_iter(..., ema=e)``.
+  The eager warm-up calls pass ``e`` on (the first ``e.update()`` builds its chunk table); the capture issues the
+  averaging launch after the Adam launches in its device-scalar form (``tsr_ema_multi_dev``), and ``1 - decay`` of each
+  replay -- ``e.decay_at(e.updates)``, so a warm-up or ``"swa"`` schedule is not frozen by the capture -- is written into
+  a static one-float device buffer before that replay.  The shadow is then the eager step's bit for bit.  The identity of
+  ``e``, its shadow address and its ``buffers`` mode are baked in: another or a re-allocated EMA recaptures.  ``ema=None``
+  (the default) captures the step as before.
 * Refused (``TactileSRHipError``): eval mode, a batch whose shape / dtype differs from the first call's, an attached
   ``GradSync`` (no collectives inside a graph), ``engine.profile`` / ``engine.debug`` / ``engine.keep_ctx``, an
   optimizer other than ``tactilesr_amd.optim.Adam``, a model not on a ROCm device, a model without a trainable
-  parameter, clipping where a trainable model parameter is not in the optimizer.
+  parameter, clipping where a trainable model parameter is not in the optimizer, a call inside ``ema.applied()``.
 """
 from __future__ import annotations
 
@@ -61,7 +68,7 @@ _CONFIG_KEYS = ("HR_scale_num", "scale_factor", "seqsCnt", "axisCnt")      # wha
 
 
 class GraphedTrainStep:
-    def __init__(self, model, optimizer, config, warmup: int = 1, clip_grad_norm: float = 0.0):
+    def __init__(self, model, optimizer, config, warmup: int = 1, clip_grad_norm: float = 0.0, ema=None):
         from .. import optim
         p0 = next(model.parameters(), None)
         if p0 is None or not p0.is_cuda:
@@ -73,9 +80,12 @@ class GraphedTrainStep:
                                     f"corrections from device memory on replay), got {type(optimizer).__name__}")
         if int(warmup) < 1:
             raise TactileSRHipError("GraphedTrainStep needs warmup >= 1 (the first backward lays out the gradient arena)")
+        if ema is not None and getattr(ema.model, "module", ema.model) is not getattr(model, "module", model):
+            raise TactileSRHipError("GraphedTrainStep: ema averages another model")
         self.model, self.optimizer, self.config = model, optimizer, config
         self.warmup = int(warmup)
         self.clip_grad_norm = float(clip_grad_norm)
+        self.ema = ema
         self.captures = 0
         self._sig = None             # (shape, dtype) of LR and HR_raw, fixed by the first call
         self._drop()
@@ -84,6 +94,7 @@ class GraphedTrainStep:
         self.graph = None
         self._out = self._launches = self._hyper = self._LR = self._HR = None
         self._norm = self._norm_work = self._norm_table = None
+        self._ema_omd = self._ema_table = None
         self._graph_key = None
         self._eager_left = self.warmup
 
@@ -99,6 +110,7 @@ class GraphedTrainStep:
                 tuple(t.data_ptr() for t in m.parameters()), tuple(b.data_ptr() for b in m.buffers()), groups,
                 tuple(self.config[k] for k in _CONFIG_KEYS), ssim_loss_config(self.config), pixel_loss_config(self.config),
                 self.clip_grad_norm,
+                (id(self.ema), self.ema._flat.data_ptr(), self.ema.buffers) if self.ema is not None else None,
                 tuple(p.requires_grad for p in m.parameters()),      # the captured backward holds the trainable set's launches
                 tuple(mod.training for mod in m.modules() if isinstance(mod, torch.nn.BatchNorm2d)))      # and each BatchNorm's mode
 
@@ -120,6 +132,8 @@ class GraphedTrainStep:
         if eng.profile is not None or eng.debug is not None or eng.keep_ctx:
             raise TactileSRHipError("GraphedTrainStep: engine.profile / engine.debug / engine.keep_ctx is on "
                                     "(host-side hooks cannot run inside a replayed graph)")
+        if self.ema is not None:
+            self.ema._not_applied("update()")      # before the replay advances any host state
         if self.clip_grad_norm > 0:
             stepped = {id(p) for g in self.optimizer.param_groups for p in g["params"]}
             if any(p.requires_grad and id(p) not in stepped for p in m.parameters()):
@@ -140,6 +154,8 @@ class GraphedTrainStep:
         if clip:                                 # {total_norm, clip_coef} and the partials of the norm kernels
             self._norm = torch.zeros(2, dtype=torch.float32, device=dev)
             self._norm_work = torch.zeros(opt_mod.GN_PARTIALS, dtype=torch.float64, device=dev)
+        if self.ema is not None:                 # 1 - decay of the replay, rewritten before each one
+            self._ema_omd = torch.zeros(1, dtype=torch.float32, device=dev)
         eng = m.train_engine()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph), torch.no_grad():
@@ -174,6 +190,8 @@ class GraphedTrainStep:
             if clip:     # _check holds: zero_grad cleared every other gradient, so fused_clip_applies(m, opt) too
                 norm_table = opt._captured_grad_norm(self.clip_grad_norm, self._norm, self._norm_work)
             launches = opt._captured_step(self._hyper, clip=self._norm[1:] if clip else None)
+            if self.ema is not None:
+                ema_table = self.ema._captured_update(self._ema_omd)
         # the launches (and the norm launch) hold the Adam chunk tables the graph reads: keep them alive with it
         out_dict = {"total_loss": loss[0]}
         pix_key = "mse_loss" if pixel_is_plain_mse(pixel) else "pixel_loss"
@@ -183,6 +201,7 @@ class GraphedTrainStep:
             out_dict["pixel_loss"] = loss[0]
         self.graph, self._out, self._launches = graph, out_dict, launches
         self._norm_table = norm_table if clip else None
+        self._ema_table = ema_table if self.ema is not None else None      # kept alive with the graph
         self._graph_key = self._key()
         self.captures += 1
 
@@ -193,7 +212,8 @@ class GraphedTrainStep:
             self._drop()
         if self.graph is None and self._eager_left > 0:
             self._eager_left -= 1
-            return train_one_iter(self.model, self.optimizer, batch, self.config, clip_grad_norm=self.clip_grad_norm)
+            return train_one_iter(self.model, self.optimizer, batch, self.config, clip_grad_norm=self.clip_grad_norm,
+                                  ema=self.ema)
         if self.graph is None:
             self._capture(LR, HR)
         self._LR.copy_(LR)
@@ -202,6 +222,9 @@ class GraphedTrainStep:
         if self._norm_table is not None:
             self.optimizer.launches += opt_mod.GN_LAUNCHES
         self._hyper[:rows.shape[0]].copy_(rows, non_blocking=True)
+        if self.ema is not None:
+            self._ema_omd.copy_(torch.tensor([self.ema._replay_scalar()], dtype=torch.float32).pin_memory(),
+                                non_blocking=True)
         self.graph.replay()
         # the graph's Adam wrote the parameters and its forward the running statistics: cached weight packs are stale
         _lib.bump_param_epoch()

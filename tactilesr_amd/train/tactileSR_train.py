@@ -87,7 +87,7 @@ def fused_clip_applies(model, optimizer) -> bool:
 
 
 def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite=False, cur_iter=None,
-                   clip_grad_norm=0.0):
+                   clip_grad_norm=0.0, ema=None):
     """zero_grad -> backward -> step, the order of cpu/trainer.py:352-361.  ``grad_sync`` (optional)
     is called between backward and step (data-parallel gradient averaging: tactilesr_amd.ddp).
 
@@ -118,6 +118,8 @@ def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite
             optimizer.step()
     else:
         optimizer.step()
+    if ema is not None:
+        ema.update()
     if check_finite:
         import math
         value = float(losses.detach())
@@ -128,14 +130,20 @@ def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite
 
 
 @torch.no_grad()
-def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=None):
+def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=None, ema=None):
     """The reference's three averages (loss, SSIM, PSNR).  ``windowed_ssim=True`` appends a fourth: the windowed SSIM
     of ``functional.ssim`` with the config's ``ssim_window`` / ``ssim_sigma`` / ``ssim_data_range`` (``ssim_loss_config``),
     averaged the same way; the first three are unchanged.
 
     ``self_ensemble`` (``None``, the default: one forward per batch, the results unchanged) names an op set of
     ``functional.self_ensemble`` -- ``"dihedral"``, ``"rot90"`` or a tuple of ops -- and scores the mean of the model's
-    outputs over those transforms of the taxels (plane by plane) instead."""
+    outputs over those transforms of the taxels (plane by plane) instead.
+
+    ``ema`` (a ``tactilesr_amd.WeightEMA`` of this model; ``None``, the default: the results unchanged) scores the
+    averaged weights: the loop runs under ``ema.applied()`` and the model's own weights are back afterwards."""
+    if ema is not None:
+        with ema.applied():
+            return eval_func(model, test_loader, config, windowed_ssim, self_ensemble)
     device = next(model.parameters()).device
     model.eval()
     tot_loss = tot_ssim = tot_psnr = tot_wssim = 0.0
