@@ -521,6 +521,42 @@ int tsr_adam_l2_multi_clip(const tsr_adam_chunk* chunks, int n_chunks, float lr,
 int tsr_adam_l2_multi_dev_clip(const tsr_adam_chunk* chunks, int n_chunks, const float* hyper, double beta1,
                                double beta2, float eps, float weight_decay, const float* clip, void* stream);
 
+/* The Adam family beyond the reference's choice, in the same one launch over a chunk table (csrc/adam_ex.hip):
+ * decoupled weight decay (torch.optim.AdamW) and AMSGrad (amsgrad=True of either torch class).  `flags` is an OR of
+ * the two bits below; flags = 0 is torch.optim.Adam's formula (tsr_adam_l2_multi's, from another kernel: the same
+ * formula, not promised the same bits).  One workgroup of 256 threads per tsr_adam_chunk record; 16-byte accesses
+ * when every pointer of the record (vmax's too, when it is used) is 16-byte aligned, scalar otherwise and for the tail.
+ * `vmax` is a DEVICE array of n_chunks pointers, one per record, already offset to the piece like the record's own
+ * pointers: torch's max_exp_avg_sq.  It is required with TSR_ADAM_AMSGRAD and must be NULL without it.
+ * Per element, with b1/b2 = (float)beta, omb = (float)(1 - beta) formed in double, and hyper4 = {lr, bc1, bc2_sqrt, decay}:
+ *   g      = clip ? g * clip[0] : g        one fp32 multiply, written back through chunk.grad unless clip[0] == 1
+ *   L2:        gg = fmaf(wd, w, g);  w0 = w
+ *   DECOUPLED: gg = g;               w0 = w * decay             (one fp32 multiply: torch's param.mul_(1 - lr * wd))
+ *   m      = b1*m + omb1*gg ;  v = b2*v + omb2*gg*gg
+ *   AMSGRAD:   vm = (v or vm is NaN) ? NaN : max(vm, v);  vhat = vm     (torch.maximum: a NaN propagates)
+ *   else:      vhat = v
+ *   p      = w0 - (lr/bc1) * (m / (sqrtf(vhat)/bc2_sqrt + eps))
+ * Every fp32 operation above is rounded on its own (the fmaf is the only fused one), in every flag combination and on
+ * both the 16-byte and the scalar path: with weight_decay = 0 the DECOUPLED and the L2 form give the same bits.
+ * tsr_adam_hyper_ex writes hyper4 to the HOST array out4: the first three are tsr_adam_hyper's floats bit for bit,
+ * decay = (float)(1.0 - (double)lr * (double)weight_decay) with TSR_ADAM_DECOUPLED and 1.0f without.
+ * tsr_adam_multi_ex forms them on the host and passes them as kernel arguments; tsr_adam_multi_ex_dev reads them from
+ * the DEVICE array hyper4, so a captured graph replays the step with the values written before that replay: same kernel
+ * body, same bits for the same floats.  `clip` (NULL: no clipping) is a DEVICE pointer to the coefficient
+ * tsr_grad_norm_multi wrote (out2 + 1).
+ * Refused with TSR_ERR_ARG before any launch: chunks NULL; n_chunks <= 0; a flag bit outside the two defined;
+ * TSR_ADAM_AMSGRAD without vmax, or vmax without it; step <= 0 (host-scalar form); hyper4 NULL (device form); out4
+ * NULL; lr, eps or weight_decay NaN or negative; a beta outside [0, 1).  A record whose n is outside 1..4096 is skipped
+ * by its workgroup: nothing is read or written through its pointers. */
+#define TSR_ADAM_DECOUPLED 1
+#define TSR_ADAM_AMSGRAD 2
+int tsr_adam_hyper_ex(float lr, double beta1, double beta2, int step, float weight_decay, int flags, float* out4);
+int tsr_adam_multi_ex(const tsr_adam_chunk* chunks, float* const* vmax, int n_chunks, int flags, float lr, double beta1,
+                      double beta2, float eps, float weight_decay, int step, const float* clip, void* stream);
+int tsr_adam_multi_ex_dev(const tsr_adam_chunk* chunks, float* const* vmax, int n_chunks, int flags,
+                          const float* hyper4, double beta1, double beta2, float eps, float weight_decay,
+                          const float* clip, void* stream);
+
 /* Weight averaging (EMA / SWA) of every tensor of a state dict in ONE launch.  `chunks` is a DEVICE array of n_chunks
  * records, one per piece of 1..4096 4-byte words of a tensor, pointers already offset to the piece: avg is the average
  * (the shadow), src the live tensor.  One workgroup of 256 threads per record; 16-byte accesses when both pointers of

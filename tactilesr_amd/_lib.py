@@ -93,6 +93,9 @@ SIGNATURES = {
     "tsr_grad_norm_multi": [_P, _I, _F, _P, _P, _P],
     "tsr_adam_l2_multi_clip": [_P, _I, _F, c_double, c_double, _F, _F, _I, _P, _P],
     "tsr_adam_l2_multi_dev_clip": [_P, _I, _P, c_double, c_double, _F, _F, _P, _P],
+    "tsr_adam_hyper_ex": [_F, c_double, c_double, _I, _F, _I, _P],
+    "tsr_adam_multi_ex": [_P, _P, _I, _I, _F, c_double, c_double, _F, _F, _I, _P, _P],
+    "tsr_adam_multi_ex_dev": [_P, _P, _I, _I, _P, c_double, c_double, _F, _F, _P, _P],
     "tsr_ema_multi": [_P, _I, _I, _F, _P],
     "tsr_ema_multi_dev": [_P, _I, _I, _P, _P],
     "tsr_psnr_ssim": [_P, _P, _I, _I, c_double, c_double, c_double, c_double, _P, _P, _P],

@@ -102,9 +102,10 @@ class GraphedTrainStep:
         """Everything the captured step bakes in (addresses and constants); lr and the step number are not."""
         m, opt = self.model, self.optimizer
         arena = m.train_engine().arena
-        groups = tuple((tuple(g["betas"]), g["eps"], g["weight_decay"],
-                        tuple((p.data_ptr(),) + ((opt.state[p]["exp_avg"].data_ptr(), opt.state[p]["exp_avg_sq"].data_ptr())
-                                                 if len(opt.state[p]) else ()) for p in g["params"]))
+        groups = tuple((tuple(g["betas"]), g["eps"], g["weight_decay"], opt._flags(g),
+                        tuple((p.data_ptr(),) + tuple(opt.state[p][k].data_ptr()
+                                                      for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq") if k in opt.state[p])
+                              for p in g["params"]))
                        for g in opt.param_groups)
         return (m.train_impl, id(arena), arena.flat.data_ptr() if arena is not None else 0,
                 tuple(t.data_ptr() for t in m.parameters()), tuple(b.data_ptr() for b in m.buffers()), groups,
@@ -147,9 +148,10 @@ class GraphedTrainStep:
         pixel = pixel_loss_config(self.config)     # refuses a bad key before anything is captured
         self._LR = torch.empty(LR.shape, dtype=LR.dtype, device=dev)
         self._HR = torch.empty(HR.shape, dtype=HR.dtype, device=dev)
-        # one row of {lr, bc1, bc2_sqrt} per Adam launch; at most one launch per parameter
-        self._hyper = torch.zeros(max(1, sum(len(g["params"]) for g in opt.param_groups)), 3, dtype=torch.float32,
-                                  device=dev)
+        # one row of {lr, bc1, bc2_sqrt} ({lr, bc1, bc2_sqrt, decay}: AdamW, AMSGrad) per Adam launch; at most one
+        # launch per parameter
+        self._hyper = torch.zeros(max(1, sum(len(g["params"]) for g in opt.param_groups)), opt.hyper_width,
+                                  dtype=torch.float32, device=dev)
         clip = self.clip_grad_norm > 0
         if clip:                                 # {total_norm, clip_coef} and the partials of the norm kernels
             self._norm = torch.zeros(2, dtype=torch.float32, device=dev)
