@@ -696,6 +696,60 @@ int tsr_gather_dihedral_wgs(const float* src, int n_src, const long long* idx, c
                             const int* cmap, const float* csign, float* out, int B, int C, int H, int W, float scale,
                             int accumulate, int max_wgs, void* stream);
 
+/* Taxel sensor-noise augmentation on the device (csrc/taxel_noise.hip): per-taxel gain drift, heteroscedastic Gaussian
+ * read-out noise and dead taxels applied to x (B,C,H,W) fp32 in one launch, driven by a counter-based generator, so the
+ * degradation of a sample is a pure function of (seed, offset, sample id, element) -- not of the batch size, the position
+ * in the batch, the grid or the code path.
+ * Generator: Philox4x32-10.  Multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57; Weyl key increments 0x9E3779B9, 0xBB67AE85;
+ * ten rounds  c' = (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)),  the key bumped after each round.
+ *   key     = (seed_lo, seed_hi)                   the two halves of the 64-bit seed
+ *   counter = (block, id, offset, tag)
+ * block: the block index inside the sample; id: ids[b] (device int64) or, with ids NULL, id_base + b; offset: a 32-bit
+ * stream number (the loader passes its epoch); tag: the effect, 0 = element noise, 1 = gain, 2 = dropout.  One block gives
+ * four words r0..r3; lane l of block j serves item 4 j + l of its effect.  An id outside [0, 2^31) makes that sample's
+ * output all-NaN and nothing else (the convention of tsr_gather_dihedral for a bad index).
+ * Effects, with P = H W, element i = c P + p of a sample, axis = c % axis_cnt (channels are frame-major, axis_cnt axes per
+ * frame, the Seqs layout), applied in this order; every fp32 operation rounds once, as written:
+ *   gain (tag 1), axis_cnt P items, item axis P + p -- shared by all frames of a sample: drift belongs to the taxel:
+ *       u = (r >> 8) 2^-24,  g = fmaf(gain_jitter, 2 u - 1, 1),  v = g x
+ *   noise (tag 0), C P items in memory order; words (r0, r1) give items 4 j and 4 j + 1, (r2, r3) items 4 j + 2 and 4 j + 3:
+ *       u1 = (2 (ra >> 9) + 1) 2^-24   (exact, never 0: |n| <= 5.77),  u2 = (rb >> 8) 2^-24
+ *       R = sqrtf(-2 logf(u1)),  n_a = R cospif(2 u2),  n_b = R sinpif(2 u2)
+ *       t = sigma_mul[axis] v,  s = sqrtf(fmaf(t, t, sigma_add[axis]^2)),  y = fmaf(s, n, v)
+ *   dropout (tag 2), P items, item p: dead when (r >> 8) < drop_thresh, drop_thresh = round(drop_prob 2^24) in [0, 2^24];
+ *       a dead taxel reads drop_value in every channel of the sample (a select: it replaces a NaN too).
+ * sigma_add, sigma_mul: HOST arrays of axis_cnt floats, passed to the kernel by value.  A neutral effect is skipped, not
+ * computed with zeros: gain_jitter == 0; both sigmas of an axis 0 (per axis); drop_thresh == 0.  With everything neutral
+ * out == x bit for bit, NaN payloads and -0 included.  A NaN or Inf in x stays in its own element.
+ * out may be x itself (in place) or disjoint from it.  One thread per four consecutive elements; 16-byte loads and stores
+ * when P % 4 == 0 and both bases are 16-byte aligned, single dwords otherwise, with the same bits.  No atomics: two
+ * launches give the same bits.
+ * Refusals (status 1, before any device call, nothing written): a NULL x, out, sigma_add or sigma_mul; B, C, H or W <= 0;
+ * axis_cnt outside 1..4 or C % axis_cnt != 0; C*H*W > 2^31 - 1; a negative or non-finite sigma; a non-finite gain_jitter
+ * or drop_value; drop_thresh outside [0, 2^24]; x and out overlapping without being equal. */
+int tsr_taxel_noise(const float* x, float* out, int B, int C, int H, int W, int axis_cnt, const float* sigma_add,
+                    const float* sigma_mul, float gain_jitter, int drop_thresh, float drop_value, const long long* ids,
+                    long long id_base, unsigned long long seed, unsigned offset, void* stream);
+/* The same launch with the caller's grid cap: at most max_wgs workgroups of 256, each walking the further work items at a
+ * stride of the grid.  The result does not depend on max_wgs, bit for bit.  tsr_taxel_noise is this with max_wgs =
+ * TSR_TAXEL_NOISE_MAX_WGS.  Refusals: those of tsr_taxel_noise, and max_wgs <= 0. */
+#define TSR_TAXEL_NOISE_MAX_WGS (1 << 20)
+int tsr_taxel_noise_wgs(const float* x, float* out, int B, int C, int H, int W, int axis_cnt, const float* sigma_add,
+                        const float* sigma_mul, float gain_jitter, int drop_thresh, float drop_value, const long long* ids,
+                        long long id_base, unsigned long long seed, unsigned offset, int max_wgs, void* stream);
+/* The same launch with the generator state read by the kernel from device memory: rng_dev points to four 32-bit words
+ * {seed_lo, seed_hi, offset, 0}.  A captured graph draws fresh noise on every replay once the host (or a kernel) rewrites
+ * the offset word (the pattern of tsr_ema_multi_dev).  The bits equal tsr_taxel_noise's for the same seed and offset.
+ * Refusals: those of tsr_taxel_noise, and a NULL rng_dev. */
+int tsr_taxel_noise_dev(const float* x, float* out, int B, int C, int H, int W, int axis_cnt, const float* sigma_add,
+                        const float* sigma_mul, float gain_jitter, int drop_thresh, float drop_value, const long long* ids,
+                        long long id_base, const unsigned* rng_dev, void* stream);
+/* The raw stream: out (B, blocks, 4) receives the four words of blocks 0 .. blocks - 1 of effect `tag` for every sample
+ * (id as above; a sample with an id outside [0, 2^31) receives the word 0x7fc00000 throughout).  This is how a caller
+ * reproduces the generator.  Refusals: a NULL out, B or blocks <= 0, a negative tag. */
+int tsr_taxel_noise_bits(unsigned* out, int B, int blocks, const long long* ids, long long id_base, int tag,
+                         unsigned long long seed, unsigned offset, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * tPSFNet (model/tPSFNet.py): batched, one workgroup per sample (the reference loops over the
  * batch in python, :118-125).  size is fixed at 100x100 depth / 99x99 PSF / 4x4 taxels, as the

@@ -103,6 +103,11 @@ SIGNATURES = {
     "tsr_pixel_loss_fwd_bwd": [_P, _P, _L, _I, c_double, _F, _F, _P, _P, _F, _I, _P, _P, _P],
     "tsr_gather_dihedral": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
     "tsr_gather_dihedral_wgs": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
+    "tsr_taxel_noise": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _I, _F, _P, _L, ctypes.c_ulonglong, ctypes.c_uint, _P],
+    "tsr_taxel_noise_wgs": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _I, _F, _P, _L, ctypes.c_ulonglong, ctypes.c_uint, _I,
+                            _P],
+    "tsr_taxel_noise_dev": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _I, _F, _P, _L, _P, _P],
+    "tsr_taxel_noise_bits": [_P, _I, _I, _P, _L, _I, ctypes.c_ulonglong, ctypes.c_uint, _P],
     "tpsf_forward": [_P, _P, _P, _P, _P, _I, _P],
     "tpsf_backward": [_P, _P, _P, _P, _P, _P, _I, _P],
     "tpsf_backward_ex": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],

@@ -22,9 +22,13 @@ def tpsf_loader(LR, depth, config, batch_size, **kw) -> DeviceSRLoader:
     """The tPSFNet trainer's loader over ``(LR, depth)`` pairs, honouring ``config["is_aug_data"]`` the way the reference's
     ``tPSFNetDataSet(..., is_aug_data=config['is_aug_data'])`` does (train/tPSFNet_train.py:31-32): set, the loader
     covers every sample under the four quarter turns (``augment="rot90", augment_mode="expand"``, the transform done on
-    the device batch by batch); unset or absent, it is the plain loader.  ``kw`` goes to ``DeviceSRLoader`` and may
-    override either choice."""
+    the device batch by batch); unset or absent, it is the plain loader.  An optional ``config["taxel_noise"]`` (a
+    ``functional.TaxelNoise`` or a dict of its fields) and ``config["taxel_noise_seed"]`` become the loader's
+    ``taxel_noise`` / ``noise_seed``; absent (or ``None``), the loader is unchanged.  ``kw`` goes to ``DeviceSRLoader`` and
+    may override any of these choices."""
     import torch
     if config.get("is_aug_data", False):
         kw = dict(dict(augment="rot90", augment_mode="expand"), **kw)
+    if config.get("taxel_noise") is not None:
+        kw = dict(dict(taxel_noise=config["taxel_noise"], noise_seed=config.get("taxel_noise_seed")), **kw)
     return DeviceSRLoader(torch.as_tensor(LR), torch.as_tensor(depth), batch_size, **kw)

@@ -32,15 +32,33 @@ class DeviceSRLoader:
     ``axis_mode="vector"`` also maps the in-plane force channels of the first tensor
     (``functional.dihedral_axis_tables``); the second tensor, ``(N,H,W)`` or ``(N,C,H,W)``, is always turned plane by
     plane.  ``last_index`` / ``last_ops`` hold the latest augmented batch's device arrays (int64 / int32).  Rank
-    sharding stays on the base samples.  The batches carry no autograd graph."""
+    sharding stays on the base samples.  The batches carry no autograd graph.
+
+    ``taxel_noise`` (default ``None``: the loader untouched, tensors and generator draws alike) is a
+    ``functional.TaxelNoise`` or a dict of its fields: every yielded first tensor then passes through one
+    ``functional.taxel_noise`` launch after the gather -- gain drift, Gaussian noise, dead taxels -- and the second tensor
+    never does.  The draws come from the launch's counter generator alone (seed ``noise_seed``, default the loader's
+    ``seed``; offset = the loader's ``epoch``, 1 during the first pass; id = the sample's index in the epoch's virtual set:
+    the sample index, or under ``"expand"`` the ``(sample, op)`` index ``j``), so the permutation and the op draws do not
+    change, and the noise of a sample in an epoch depends neither on the batch size nor on where shuffling puts it.  Ids
+    count within a rank's shard: give each rank its own ``noise_seed``."""
 
     def __init__(self, LR: torch.Tensor, HR: torch.Tensor, batch_size: int, shuffle: bool = False,
                  drop_last: bool = False, seed: Optional[int] = None, device="cuda",
                  rank: int = 0, world_size: int = 1, augment=None, augment_mode: str = "random",
-                 axis_mode: str = "planes", axis_cnt: int = 3):
+                 axis_mode: str = "planes", axis_cnt: int = 3, taxel_noise=None, noise_seed: Optional[int] = None):
         assert LR.shape[0] == HR.shape[0], "LR and HR must hold the same number of samples"
         self._ops = None
         self.last_index = self.last_ops = None
+        self._noise = None
+        if taxel_noise is not None:
+            from .. import functional as Fh
+            from .._lib import TactileSRHipError
+            self._noise = Fh.taxel_noise_spec(taxel_noise)
+            if LR.dim() != 4 or LR.dtype != torch.float32 or LR.shape[1] % self._noise.axis_cnt:
+                raise TactileSRHipError("taxel noise needs a (N,C,H,W) fp32 first tensor with C a multiple of the spec's "
+                                        f"axis_cnt, got {tuple(LR.shape)} {LR.dtype}")
+            self.noise_seed = int(noise_seed) if noise_seed is not None else (0 if seed is None else int(seed))
         if augment is not None:
             from .. import functional as Fh
             from .._lib import TactileSRHipError
@@ -113,24 +131,35 @@ class DeviceSRLoader:
             index = order
             ops = self._ops_t[torch.randint(0, n_ops, (n,), generator=self._gen, device=dev)]
         self.epoch += 1
+        epoch = self.epoch
         for i in range(len(self)):
             lo, hi = i * self.batch_size, min(n, (i + 1) * self.batch_size)
             idx, op = index[lo:hi].contiguous(), ops[lo:hi].contiguous()
             self.last_index, self.last_ops = idx, op
-            yield (Fh.dihedral(self.LR, op, idx, axis_mode=self.axis_mode, op_mask=self._op_mask, tables=self._tables),
-                   Fh.dihedral(self.HR, op, idx, op_mask=self._op_mask))
+            lr = Fh.dihedral(self.LR, op, idx, axis_mode=self.axis_mode, op_mask=self._op_mask, tables=self._tables)
+            if self._noise is not None:                                 # the virtual index: (sample, op) pairs differ under "expand"
+                Fh.taxel_noise(lr, self._noise, self.noise_seed, epoch, ids=order[lo:hi], out=lr)
+            yield lr, Fh.dihedral(self.HR, op, idx, op_mask=self._op_mask)
 
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         if self._ops is not None:
             yield from self._iter_augmented()
             return
+        if self._noise is not None:
+            from .. import functional as Fh
         n = self.LR.shape[0]
         order = torch.randperm(n, generator=self._gen, device=self.LR.device) if self.shuffle else None
         self.epoch += 1
+        epoch = self.epoch
         for i in range(len(self)):
             lo, hi = i * self.batch_size, min(n, (i + 1) * self.batch_size)
             if order is None:
-                yield self.LR[lo:hi], self.HR[lo:hi]
+                lr, hr = self.LR[lo:hi], self.HR[lo:hi]
+                if self._noise is not None:                             # out of place: the set itself stays clean
+                    lr = Fh.taxel_noise(lr, self._noise, self.noise_seed, epoch, id_base=lo)
             else:
                 idx = order[lo:hi]
-                yield self.LR.index_select(0, idx), self.HR.index_select(0, idx)
+                lr, hr = self.LR.index_select(0, idx), self.HR.index_select(0, idx)
+                if self._noise is not None:
+                    Fh.taxel_noise(lr, self._noise, self.noise_seed, epoch, ids=idx, out=lr)
+            yield lr, hr

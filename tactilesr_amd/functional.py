@@ -4,6 +4,10 @@ train/tactileSR_train.py:41-51,66-101; utility/tools.py:49-114), and the pixel l
 (L1 / Charbonnier / Huber: not in the reference, whose criterion is nn.MSELoss)."""
 from __future__ import annotations
 
+import ctypes
+import dataclasses as _dc
+import math as _math
+
 import torch
 
 from ._lib import call, ptr, stream, c_int as _I, c_float as _F, c_longlong as _L, c_double as _D, TactileSRHipError
@@ -477,3 +481,269 @@ def self_ensemble(model, LR: torch.Tensor, ops="dihedral", axis_mode: str = "pla
     finally:
         model.train(was_training)
     return acc
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Taxel sensor noise (tsr_taxel_noise, csrc/taxel_noise.hip): gain drift, heteroscedastic Gaussian noise and dead taxels in
+# one launch from a counter-based generator.  A data path like `dihedral`: not differentiable, no autograd graph.
+# ----------------------------------------------------------------------------------------------------------------------
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+TAXEL_NOISE_TAGS = {"noise": 0, "gain": 1, "dropout": 2}
+
+
+def _f32(v) -> float:
+    import numpy as np
+    return float(np.float32(v))
+
+
+@_dc.dataclass(frozen=True)
+class TaxelNoise:
+    """The degradation of ``taxel_noise`` (formulas: include/tactilesr_hip.h).  ``sigma_add`` / ``sigma_mul`` are a scalar
+    or one value per axis (``axis_cnt`` of them; channel ``c`` is axis ``c % axis_cnt``): the noise of an element ``v`` has
+    standard deviation ``sqrt(sigma_add^2 + (sigma_mul v)^2)``.  ``gain_jitter`` scales every physical taxel (shared by the
+    frames of a sample) by a factor uniform in ``1 +- gain_jitter``; ``drop_prob`` is the share of dead taxels, which read
+    ``drop_value`` in every channel.  Frozen; validated on construction (``TactileSRHipError``); the values are held as the
+    fp32 numbers the kernel receives."""
+    sigma_add: object = 0.0
+    sigma_mul: object = 0.0
+    gain_jitter: float = 0.0
+    drop_prob: float = 0.0
+    drop_value: float = 0.0
+    axis_cnt: int = 3
+
+    def __post_init__(self):
+        a = self.axis_cnt
+        if isinstance(a, bool) or not isinstance(a, int) or not 1 <= a <= 4:
+            raise TactileSRHipError(f"TaxelNoise: axis_cnt must be an integer in 1..4, got {a!r}")
+
+        def sig(name, v):
+            try:
+                vals = tuple(_f32(s) for s in v) if hasattr(v, "__len__") else (_f32(v),) * a
+            except (TypeError, ValueError):
+                raise TactileSRHipError(f"TaxelNoise: {name} must be a number or {a} numbers, got {v!r}") from None
+            if len(vals) != a:
+                raise TactileSRHipError(f"TaxelNoise: {name} needs one value or one per axis ({a}), got {len(vals)}")
+            if not all(_math.isfinite(s) and s >= 0.0 for s in vals):
+                raise TactileSRHipError(f"TaxelNoise: {name} must be finite and >= 0, got {vals}")
+            return vals
+        object.__setattr__(self, "sigma_add", sig("sigma_add", self.sigma_add))
+        object.__setattr__(self, "sigma_mul", sig("sigma_mul", self.sigma_mul))
+        for name in ("gain_jitter", "drop_prob", "drop_value"):
+            try:
+                v = _f32(getattr(self, name)) if name != "drop_prob" else float(getattr(self, name))
+            except (TypeError, ValueError):
+                raise TactileSRHipError(f"TaxelNoise: {name} must be a number, got {getattr(self, name)!r}") from None
+            if not _math.isfinite(v):
+                raise TactileSRHipError(f"TaxelNoise: {name} must be finite, got {v}")
+            object.__setattr__(self, name, v)
+        if not 0.0 <= self.drop_prob <= 1.0:
+            raise TactileSRHipError(f"TaxelNoise: drop_prob must lie in [0, 1], got {self.drop_prob}")
+
+    @property
+    def drop_thresh(self) -> int:
+        """``round(drop_prob 2^24)``: a taxel is dead when the top 24 bits of its word are below it."""
+        return int(_math.floor(self.drop_prob * (1 << 24) + 0.5))
+
+    @property
+    def is_identity(self) -> bool:
+        """Every effect neutral: the launch copies ``x`` bit for bit."""
+        return (self.gain_jitter == 0.0 and self.drop_thresh == 0
+                and all(s == 0.0 for s in self.sigma_add + self.sigma_mul))
+
+
+def taxel_noise_spec(obj):
+    """A ``TaxelNoise`` from a ``TaxelNoise`` (itself), a dict of its fields, or ``None`` (stays ``None``: no noise)."""
+    if obj is None or isinstance(obj, TaxelNoise):
+        return obj
+    if isinstance(obj, dict):
+        try:
+            return TaxelNoise(**obj)
+        except TypeError as e:
+            raise TactileSRHipError(f"taxel noise spec: {e}") from None
+    raise TactileSRHipError(f"a taxel noise spec is a TaxelNoise, a dict of its fields or None, got {type(obj).__name__}")
+
+
+def _philox_np(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on broadcastable uint64 arrays holding 32-bit values: the four output words, as uint64."""
+    import numpy as np
+    m32 = np.uint64(0xffffffff)
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) for c in (c0, c1, c2, c3))
+    k0, k1 = np.uint64(k0), np.uint64(k1)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c0, np.uint64(_PHILOX_M1) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(_PHILOX_W0)) & m32, (k1 + np.uint64(_PHILOX_W1)) & m32
+    return c0, c1, c2, c3
+
+
+def _taxel_words_np(ids, blocks, tag, seed, offset):
+    """(B, 4 blocks) uint32 words of effect ``tag`` for the sample ids (a numpy int64 array; bad ids are the caller's)."""
+    import numpy as np
+    j = np.arange(blocks, dtype=np.uint64)[None, :]
+    i = np.asarray(ids).astype(np.uint64)[:, None]
+    seed = int(seed) & 0xffffffffffffffff
+    w = _philox_np(j, i, np.uint64(offset), np.uint64(tag), seed & 0xffffffff, seed >> 32)
+    return np.stack(np.broadcast_arrays(*w), -1).reshape(len(ids), 4 * blocks).astype(np.uint32)
+
+
+def _cossinpi_f32(a):
+    """cos(pi a), sin(pi a) for fp32 ``a`` in [0, 2) on a grid of 2^-23: the quarter is taken off exactly, so the argument
+    of cos / sin carries one rounding of pi r with |r| <= 1/4."""
+    import numpy as np
+    k = np.floor(a * np.float32(2.0) + np.float32(0.5))
+    r = (a - k * np.float32(0.5)).astype(np.float32)
+    t = np.float32(np.pi) * r
+    c, s = np.cos(t), np.sin(t)
+    q = k.astype(np.int64) & 3
+    return (np.choose(q, [c, -s, -c, s]).astype(np.float32), np.choose(q, [s, c, -s, -c]).astype(np.float32))
+
+
+def _taxel_noise_np(x, spec: TaxelNoise, seed, offset, ids):
+    """The fp32 restatement of csrc/taxel_noise.hip in numpy (CPU tensors): the same Philox stream and formulas; an fma is
+    taken in fp64 and rounded.  Within a few ulp of the device, not bit-equal (libm's logf / cos / sin)."""
+    import numpy as np
+    B, C, H, W = x.shape
+    P, a = H * W, spec.axis_cnt
+    f32 = np.float32
+    ids = np.asarray(ids, dtype=np.int64)
+    bad = (ids < 0) | (ids > 0x7fffffff)
+    safe = np.where(bad, 0, ids)
+    v = x.reshape(B, C // a, a, P).copy()
+    two24 = f32(2.0 ** -24)
+    if spec.gain_jitter != 0.0:
+        w = _taxel_words_np(safe, (a * P + 3) // 4, 1, seed, offset)[:, :a * P].reshape(B, 1, a, P)
+        u2m1 = f32(2.0) * ((w >> 8).astype(f32) * two24) - f32(1.0)
+        g = (1.0 + np.float64(f32(spec.gain_jitter)) * u2m1.astype(np.float64)).astype(f32)
+        with np.errstate(invalid="ignore", over="ignore"):
+            v = (g * v).astype(f32)
+    active = np.array([spec.sigma_add[k] != 0.0 or spec.sigma_mul[k] != 0.0 for k in range(a)])
+    if active.any():
+        nb = (C * P + 3) // 4
+        w = _taxel_words_np(safe, nb, 0, seed, offset).reshape(B, nb, 2, 2)
+        u1 = (f32(2.0) * (w[..., 0] >> 9).astype(f32) + f32(1.0)) * two24
+        a2 = (w[..., 1] >> 8).astype(f32) * f32(2.0 ** -23)
+        R = np.sqrt(f32(-2.0) * np.log(u1)).astype(f32)
+        c, s = _cossinpi_f32(a2)
+        n = np.stack([R * c, R * s], -1).astype(f32).reshape(B, 4 * nb)[:, :C * P].reshape(B, C // a, a, P)
+        sa = np.asarray(spec.sigma_add, f32).reshape(1, 1, a, 1)
+        sm = np.asarray(spec.sigma_mul, f32).reshape(1, 1, a, 1)
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = (sm * v).astype(f32)
+            sd = np.sqrt((t.astype(np.float64) * t + (sa * sa).astype(np.float64)).astype(f32))
+            y = (v.astype(np.float64) + sd.astype(np.float64) * n).astype(f32)
+        v = np.where(active.reshape(1, 1, a, 1), y, v)
+    v = v.reshape(B, C, P)
+    if spec.drop_thresh != 0:
+        w = _taxel_words_np(safe, (P + 3) // 4, 2, seed, offset)[:, :P]
+        v = np.where(((w >> 8) < np.uint32(spec.drop_thresh))[:, None, :], f32(spec.drop_value), v)
+    v = np.ascontiguousarray(v, dtype=f32)
+    if bad.any():
+        v.view(np.uint32)[bad] = 0x7fc00000
+    return v.reshape(B, C, H, W)
+
+
+def _rng_words(seed, offset):
+    seed, offset = int(seed) & 0xffffffffffffffff, int(offset)
+    if not 0 <= offset <= 0xffffffff:
+        raise TactileSRHipError(f"taxel noise: offset must lie in [0, 2^32), got {offset}")
+    return seed, offset
+
+
+def taxel_noise_rng(seed: int = 0, offset: int = 0, device="cuda") -> torch.Tensor:
+    """The four int32 words ``{seed_lo, seed_hi, offset, 0}`` of ``taxel_noise(rng=...)`` on ``device``.  Rewrite word 2
+    (``rng[2] = new_offset``, or ``copy_`` from a host tensor) between the replays of a captured graph."""
+    seed, offset = _rng_words(seed, offset)
+    import numpy as np
+    return torch.from_numpy(np.array([seed & 0xffffffff, seed >> 32, offset, 0], dtype=np.uint32).view(np.int32)).to(device)
+
+
+def taxel_noise(x: torch.Tensor, spec, seed: int = 0, offset: int = 0, ids=None, id_base: int = 0, out=None,
+                rng=None) -> torch.Tensor:
+    """Degrade the taxels ``x`` ``(B, C, H, W)`` fp32 with ``spec`` (a ``TaxelNoise``, a dict of its fields, or ``None`` =
+    the identity) in one ``tsr_taxel_noise`` launch: gain drift, then Gaussian noise, then dead taxels (formulas:
+    ``TaxelNoise`` and include/tactilesr_hip.h).  The draws come from Philox4x32-10 with key ``seed`` (64 bits; a larger or
+    negative value is taken modulo 2^64) and counter ``(block, id, offset, tag)``: the noise of a sample is a pure function
+    of ``(seed, offset, id, element)``.  ``id`` is ``ids[b]`` (an int64 tensor or a sequence) or ``id_base + b``; an id
+    outside ``[0, 2^31)`` gives an all-NaN sample.  ``out`` may be ``x`` itself (in place) or a disjoint tensor.  ``rng`` -- a
+    device int32 / uint32 tensor of the 4 words ``{seed_lo, seed_hi, offset, 0}`` (``taxel_noise_rng``) -- replaces
+    ``seed`` / ``offset`` and is read by the kernel (``tsr_taxel_noise_dev``), so a captured graph draws fresh noise on each
+    replay after the offset word is rewritten.  No host synchronisation on a ROCm tensor.  A CPU tensor runs a numpy fp32
+    restatement of the same stream and formulas (within a few ulp of the device, not bit-equal).  Not differentiable: a
+    data path, it carries no autograd graph."""
+    spec = taxel_noise_spec(spec) or TaxelNoise()
+    if x.dim() != 4:
+        raise TactileSRHipError(f"taxel_noise needs (B,C,H,W), got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise TactileSRHipError(f"taxel_noise needs fp32 taxels, got {x.dtype}")
+    x = x.detach()
+    B, C, H, W = x.shape
+    if B == 0 or C == 0 or H == 0 or W == 0:
+        raise TactileSRHipError(f"taxel_noise: an empty tensor {tuple(x.shape)}")
+    if C % spec.axis_cnt:
+        raise TactileSRHipError(f"taxel_noise: {C} channels are no multiple of axis_cnt = {spec.axis_cnt}")
+    seed, offset = _rng_words(seed, offset)
+    if ids is not None:
+        ids = torch.as_tensor(ids, device=x.device).to(torch.int64).contiguous()
+        if ids.shape != (B,):
+            raise TactileSRHipError(f"taxel_noise: ids must hold one id per sample ({B}), got {tuple(ids.shape)}")
+    if rng is not None:
+        if (not isinstance(rng, torch.Tensor) or rng.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
+                or rng.numel() != 4 or rng.device != x.device or not rng.is_contiguous()):
+            raise TactileSRHipError("taxel_noise: rng must be a contiguous int32 / uint32 tensor of 4 words on x's device")
+    if out is not None:
+        if tuple(out.shape) != (B, C, H, W) or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+            raise TactileSRHipError("taxel_noise: out must be contiguous with x's shape, dtype and device")
+        same = x.is_contiguous() and out.data_ptr() == x.data_ptr()
+        if not same and _memory_overlaps(x, out):
+            raise TactileSRHipError("taxel_noise: out overlaps x in memory without being x")
+    if not x.is_cuda:
+        import numpy as np
+        if rng is not None:
+            w = rng.view(torch.int32).numpy().view(np.uint32)
+            seed, offset = int(w[0]) | (int(w[1]) << 32), int(w[2])
+        idn = ids.numpy() if ids is not None else np.arange(B, dtype=np.int64) + int(id_base)
+        res = torch.from_numpy(_taxel_noise_np(x.contiguous().numpy(), spec, seed, offset, idn))
+        if out is None:
+            return res
+        out.copy_(res)
+        return out
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    n = spec.axis_cnt
+    sa, sm = (ctypes.c_float * n)(*spec.sigma_add), (ctypes.c_float * n)(*spec.sigma_mul)
+    head = (ptr(x), ptr(out), _I(B), _I(C), _I(H), _I(W), _I(n), ctypes.cast(sa, ctypes.c_void_p),
+            ctypes.cast(sm, ctypes.c_void_p), _F(spec.gain_jitter), _I(spec.drop_thresh), _F(spec.drop_value), ptr(ids),
+            _L(int(id_base)))
+    if rng is not None:
+        call("tsr_taxel_noise_dev", *head, ptr(rng), stream())
+    else:
+        call("tsr_taxel_noise", *head, ctypes.c_ulonglong(seed), ctypes.c_uint(offset), stream())
+    return out
+
+
+def taxel_noise_bits(B: int, blocks: int, tag: int, seed: int = 0, offset: int = 0, ids=None, id_base: int = 0,
+                     device="cuda") -> torch.Tensor:
+    """The raw Philox stream of ``taxel_noise``: an int32 tensor ``(B, blocks, 4)`` holding the bit patterns of the words of
+    blocks ``0 .. blocks - 1`` of effect ``tag`` (0 noise, 1 gain, 2 dropout) for samples ``ids[b]`` or ``id_base + b``
+    (``tsr_taxel_noise_bits``; numpy on ``device="cpu"``).  A sample with an id outside ``[0, 2^31)`` holds 0x7fc00000."""
+    B, blocks, tag = int(B), int(blocks), int(tag)
+    if B <= 0 or blocks <= 0 or not 0 <= tag <= 0x7fffffff:
+        raise TactileSRHipError(f"taxel_noise_bits: B and blocks must be positive and tag in [0, 2^31), got {B}, {blocks}, {tag}")
+    seed, offset = _rng_words(seed, offset)
+    dev = torch.device(device)
+    if ids is not None:
+        ids = torch.as_tensor(ids, device=dev).to(torch.int64).contiguous()
+        if ids.shape != (B,):
+            raise TactileSRHipError(f"taxel_noise_bits: ids must hold one id per sample ({B}), got {tuple(ids.shape)}")
+    if dev.type != "cuda":
+        import numpy as np
+        idn = ids.numpy() if ids is not None else np.arange(B, dtype=np.int64) + int(id_base)
+        bad = (idn < 0) | (idn > 0x7fffffff)
+        w = _taxel_words_np(np.where(bad, 0, idn), blocks, tag, seed, offset)
+        w[bad] = 0x7fc00000
+        return torch.from_numpy(w.view(np.int32).reshape(B, blocks, 4).copy())
+    out = torch.empty(B, blocks, 4, dtype=torch.int32, device=dev)
+    call("tsr_taxel_noise_bits", ptr(out), _I(B), _I(blocks), ptr(ids), _L(int(id_base)), _I(tag), ctypes.c_ulonglong(seed),
+         ctypes.c_uint(offset), stream())
+    return out

@@ -130,7 +130,8 @@ def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite
 
 
 @torch.no_grad()
-def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=None, ema=None):
+def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=None, ema=None, taxel_noise=None,
+              noise_seed=0):
     """The reference's three averages (loss, SSIM, PSNR).  ``windowed_ssim=True`` appends a fourth: the windowed SSIM
     of ``functional.ssim`` with the config's ``ssim_window`` / ``ssim_sigma`` / ``ssim_data_range`` (``ssim_loss_config``),
     averaged the same way; the first three are unchanged.
@@ -140,10 +141,18 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
     outputs over those transforms of the taxels (plane by plane) instead.
 
     ``ema`` (a ``tactilesr_amd.WeightEMA`` of this model; ``None``, the default: the results unchanged) scores the
-    averaged weights: the loop runs under ``ema.applied()`` and the model's own weights are back afterwards."""
+    averaged weights: the loop runs under ``ema.applied()`` and the model's own weights are back afterwards.
+
+    ``taxel_noise`` (a ``functional.TaxelNoise`` or a dict of its fields; ``None``, the default: the results unchanged)
+    scores the model on degraded taxels: after ``_prep`` each batch's ``LR`` passes through one
+    ``functional.taxel_noise`` launch with seed ``noise_seed``, offset 0 and ``id_base`` = the number of samples seen so
+    far, so sample ``k`` of the set always meets the same noise -- the score is deterministic and does not depend on the
+    loader's batch size (beyond the averaging over batches itself).  It composes with ``self_ensemble`` and ``ema``."""
     if ema is not None:
         with ema.applied():
-            return eval_func(model, test_loader, config, windowed_ssim, self_ensemble)
+            return eval_func(model, test_loader, config, windowed_ssim, self_ensemble, None, taxel_noise, noise_seed)
+    noise = Fh.taxel_noise_spec(taxel_noise)
+    seen = 0
     device = next(model.parameters()).device
     model.eval()
     tot_loss = tot_ssim = tot_psnr = tot_wssim = 0.0
@@ -151,6 +160,9 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
     _, window, sigma, data_range = ssim_loss_config(config)
     for batch in test_loader:
         LR, HR = _prep(batch, config, device)
+        if noise is not None:
+            LR = Fh.taxel_noise(LR, noise, noise_seed, 0, id_base=seen)
+            seen += LR.shape[0]
         out = model(LR) if self_ensemble is None else Fh.self_ensemble(model, LR.contiguous(), self_ensemble)
         tot_loss += float(Fh.mse_loss(out, HR))
         ps, ss = Fh.psnr_ssim(out, HR, config["sensorMaxVaule_factor"], reference_quirk=True)
