@@ -651,6 +651,51 @@ int tsr_pixel_loss_fwd_bwd(const float* y, const float* t, long long n, int kind
                            float fg_threshold, float* loss, float* dy, float dy_scale, int accumulate, float* dt,
                            double* work, void* stream);
 
+/* Degradation-consistency loss (csrc/degrade_loss.hip): the sensor model's pooling of an image onto the 4x4 taxels
+ * (reference model/tPSFNet.py:129-141, degradation_process: Gaussian masks around the taxel centres, scaled to (0, 1)),
+ * generalised from the 100x100 grid to any H x W, the mean squared residual against measured taxels z, and its gradients
+ * with respect to the image and to z, from one launch.  For image b with width gamma in (0, 1e6]:
+ *   KM = 100/15138,  c_a = 12 + 25 a (a = 0..3),  mn = exp(-100/gamma)
+ *   X(x) = (x + 0.5) 100/H - 0.5,  Y(v) = (v + 0.5) 100/W - 0.5     the pixel centres of F.interpolate(align_corners=False)
+ *   E_a[x] = exp(-KM (X(x) - c_a)^2 / gamma),  F_c[v] = exp(-KM (Y(v) - c_c)^2 / gamma)
+ *   k = gain 1e-4 (100/H)(100/W) / (1 - mn)
+ *   D_ac = k (sum_xv E_a[x] y_xv F_c[v] - mn sum_xv y_xv)           lr_deg[b][4a + c]; H = W = 100, gain 1: the reference's
+ *   r_ac = D_ac - z_ac,  q[b] = (1/16) sum_ac r_ac^2
+ *   dq/dy_xv = (2/16) k (sum_ac r_ac E_a[x] F_c[v] - mn sum_ac r_ac),  dq/dz_ac = -(2/16) r_ac
+ * The upper limit TSR_DEGRADE_GAMMA_MAX = 1e6 is where the operator stops meaning anything, well before it stops being
+ * computable: as gamma grows every mask tends to the constant 1 and D to the difference of two nearly equal sums over a
+ * vanishing 1 - mn (from about 1e18 on 1 - mn rounds to 0 and k is Inf).  At 1e6 the masks vary by 1e-4 over the sensor,
+ * far flatter than any width the sensor model is trained to (a few tens at most), and 1 - mn still carries twelve digits.
+ * gamma is not differentiated.  gain undoes a scaling of the image (the train step's target is HR / HR_scale_num).
+ * y (B,1,H,W) fp32 contiguous, 1 <= H, W <= 128.  z: taxel (a,c) of image b at z[b z_bstride + 4a + c], so a channel slice
+ * of a (B,C,4,4) tensor is passed in place; NULL = the forward alone (q, dy, dz must then be NULL and lr_deg given).
+ * gamma_dev (B) on the device, NULL = gamma_all for every image; where gamma_dev[b] == gamma_all the bits are those of the
+ * NULL form.  lr_deg (B,16) optional.  q (B), required with z.  dy (B,1,H,W) optional, the contract of tsr_ssim_fwd_bwd:
+ * dy = dy_scale dq/dy when accumulate = 0, dy += the same when accumulate = 1; it must not overlap y.  dz (B,16) optional,
+ * always overwritten with dy_scale dq/dz.
+ * Arithmetic: the tables, every sum, r and the gradients are fp64 from the exact fp32 inputs; a value is rounded to fp32
+ * once, at its store.  One workgroup per image, at most TSR_DEGRADE_MAX_WGS of them walking the batch; the 16 + 1 sums are
+ * reduced in a fixed order and there are no atomics: two launches give the same bits.  The image is read once (the gradient
+ * needs r and the tables only).  float4 loads when W % 4 == 0 and y is 16-byte aligned, float4 stores when W % 4 == 0 and dy
+ * is; otherwise the same four columns move one float at a time through the same arithmetic, with the same bits.
+ * Non-finite input: images are independent.  A NaN or Inf pixel makes its own image's lr_deg, q and whole dy non-finite
+ * (the mn sum y term reaches every taxel).  A device gamma that is <= 0, NaN or above 1e6 (Inf included) makes that image's lr_deg, q, dz and dy
+ * all-NaN (dy whatever accumulate says), never an out-of-range access.  Every other image keeps the bits of the clean run.
+ * Refusals (status 1, before any device call, nothing written): a NULL y; B, H or W <= 0; H or W > 128; gamma_dev NULL with
+ * gamma_all <= 0, NaN or above 1e6 (Inf included); gain NaN or Inf; z without q; z NULL with q, dy or dz given or without lr_deg; z_bstride < 16
+ * with B > 1; accumulate not 0 or 1; accumulate = 1 without dy; dy_scale NaN; dy overlapping y. */
+#define TSR_DEGRADE_MAX_WGS 2048
+#define TSR_DEGRADE_GAMMA_MAX 1e6
+int tsr_degrade_fwd_bwd(const float* y, int B, int H, int W, const float* z, long long z_bstride, const float* gamma_dev,
+                        double gamma_all, double gain, float* lr_deg, float* q, float* dy, float dy_scale, int accumulate,
+                        float* dz, void* stream);
+/* The same launch with the caller's grid cap (tsr_degrade_fwd_bwd is this with max_wgs = TSR_DEGRADE_MAX_WGS): at most
+ * max_wgs workgroups, each walking the further images at a stride of the grid.  The result does not depend on max_wgs,
+ * bit for bit.  Refusals: those above, and max_wgs < 1. */
+int tsr_degrade_fwd_bwd_wgs(const float* y, int B, int H, int W, const float* z, long long z_bstride,
+                            const float* gamma_dev, double gamma_all, double gain, float* lr_deg, float* q, float* dy,
+                            float dy_scale, int accumulate, float* dz, int max_wgs, void* stream);
+
 /* Rot90 / flip augmentation on the device (csrc/dihedral.hip; the reference's augmentData, utility/raw_data_process.py:57-95,
  * without storing four copies, plus the mirrored half of the dihedral group): gather sample idx[b] of src and write it
  * transformed, in one pass and one launch.

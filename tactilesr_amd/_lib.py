@@ -101,6 +101,8 @@ SIGNATURES = {
     "tsr_psnr_ssim": [_P, _P, _I, _I, c_double, c_double, c_double, c_double, _P, _P, _P],
     "tsr_ssim_fwd_bwd": [_P, _P, _I, _I, _I, _I, c_double, c_double, c_double, _P, _P, _F, _I, _P],
     "tsr_pixel_loss_fwd_bwd": [_P, _P, _L, _I, c_double, _F, _F, _P, _P, _F, _I, _P, _P, _P],
+    "tsr_degrade_fwd_bwd": [_P, _I, _I, _I, _P, _L, _P, c_double, c_double, _P, _P, _P, _F, _I, _P, _P],
+    "tsr_degrade_fwd_bwd_wgs": [_P, _I, _I, _I, _P, _L, _P, c_double, c_double, _P, _P, _P, _F, _I, _P, _I, _P],
     "tsr_gather_dihedral": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
     "tsr_gather_dihedral_wgs": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
     "tsr_taxel_noise": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _I, _F, _P, _L, ctypes.c_ulonglong, ctypes.c_uint, _P],

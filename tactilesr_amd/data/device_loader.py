@@ -41,15 +41,29 @@ class DeviceSRLoader:
     ``seed``; offset = the loader's ``epoch``, 1 during the first pass; id = the sample's index in the epoch's virtual set:
     the sample index, or under ``"expand"`` the ``(sample, op)`` index ``j``), so the permutation and the op draws do not
     change, and the noise of a sample in an epoch depends neither on the batch size nor on where shuffling puts it.  Ids
-    count within a rank's shard: give each rank its own ``noise_seed``."""
+    count within a rank's shard: give each rank its own ``noise_seed``.
+
+    ``gamma`` (default ``None``: the loader as it was, batches and generator draws alike) is an optional (N,) tensor of
+    per-sample mask widths (the datasets' ``alphaBeta[2]``) for the degradation-consistency loss.  It is gathered with
+    each batch's sample indices -- plain, shuffled, augmented and ``"expand"`` alike; the dihedral ops leave it alone,
+    the taxel centres being mirror-symmetric -- and yielded as a third element, ``(LR, HR, gamma)``, which
+    ``train_one_iter`` / ``eval_func`` / ``GraphedTrainStep`` accept.  With it ``last_index`` is also kept by the plain
+    loader."""
 
     def __init__(self, LR: torch.Tensor, HR: torch.Tensor, batch_size: int, shuffle: bool = False,
                  drop_last: bool = False, seed: Optional[int] = None, device="cuda",
                  rank: int = 0, world_size: int = 1, augment=None, augment_mode: str = "random",
-                 axis_mode: str = "planes", axis_cnt: int = 3, taxel_noise=None, noise_seed: Optional[int] = None):
+                 axis_mode: str = "planes", axis_cnt: int = 3, taxel_noise=None, noise_seed: Optional[int] = None,
+                 gamma: Optional[torch.Tensor] = None):
         assert LR.shape[0] == HR.shape[0], "LR and HR must hold the same number of samples"
+        if gamma is not None:
+            from .._lib import TactileSRHipError
+            gamma = torch.as_tensor(gamma)
+            if gamma.dim() != 1 or gamma.shape[0] != LR.shape[0]:
+                raise TactileSRHipError(f"gamma must hold one value per sample, ({LR.shape[0]},), got {tuple(gamma.shape)}")
+            gamma = gamma.float()
         self._ops = None
-        self.last_index = self.last_ops = None
+        self.last_index = self.last_ops = self._arange = None
         self._noise = None
         if taxel_noise is not None:
             from .. import functional as Fh
@@ -87,8 +101,11 @@ class DeviceSRLoader:
             from ..ddp import equal_shard
             idx = torch.as_tensor(equal_shard(n, rank, world_size), dtype=torch.long)
             LR, HR = LR.index_select(0, idx.to(LR.device)), HR.index_select(0, idx.to(HR.device))
+            if gamma is not None:
+                gamma = gamma.index_select(0, idx.to(gamma.device))
         self.LR = LR.to(dev).contiguous()
         self.HR = HR.to(dev).contiguous()
+        self.gamma = gamma.to(dev).contiguous() if gamma is not None else None
         self.batch_size, self.shuffle, self.drop_last = int(batch_size), bool(shuffle), bool(drop_last)
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(0 if seed is None else int(seed))
@@ -99,23 +116,33 @@ class DeviceSRLoader:
                 self._tables = tuple(t.to(dev) for t in self._tables)
 
     @classmethod
-    def from_entries(cls, entries: List[list], batch_size: int, **kw) -> "DeviceSRLoader":
-        """From the generator's in-memory entries (tactilesr_amd.data.depth2tactile.synthesize)."""
+    def from_entries(cls, entries: List[list], batch_size: int, with_gamma: bool = False, **kw) -> "DeviceSRLoader":
+        """From the generator's in-memory entries (tactilesr_amd.data.depth2tactile.synthesize).  ``with_gamma=True``
+        also reads each sample's mask width ``alphaBeta[2]`` (data/SRdataset/depth2tactile.py:114-119) into ``gamma``."""
         LR = torch.stack([torch.as_tensor(e[0]["LR"]) for e in entries])
         HR = torch.stack([torch.as_tensor(e[0]["HR"]) for e in entries])
+        if with_gamma:                           # the third entry of the generator's alphaBeta row is the mask width
+            kw["gamma"] = torch.tensor([float(np.asarray(e[0]["alphaBeta"]).reshape(-1)[2]) for e in entries],
+                                       dtype=torch.float32)
         return cls(LR, HR, batch_size, **kw)
 
     @classmethod
-    def from_file(cls, path: str, batch_size: int, **kw) -> "DeviceSRLoader":
+    def from_file(cls, path: str, batch_size: int, with_gamma: bool = False, **kw) -> "DeviceSRLoader":
         """From a dataset file in the reference's on-disk format (an object ``.npy`` of ``{'LR','HR',...}`` dicts)
         written by ``save_dataset``.  Object arrays are pickles: only load files you wrote."""
         arr = np.load(path, allow_pickle=True)
         entries = [[arr[i].item() if arr[i].shape == () else arr[i, 0]] for i in range(len(arr))]
-        return cls.from_entries(entries, batch_size, **kw)
+        return cls.from_entries(entries, batch_size, with_gamma=with_gamma, **kw)
 
     def __len__(self) -> int:
         n = self._virtual_len()
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def _identity(self) -> torch.Tensor:
+        """0 .. N-1 on the device, built once: what the unshuffled loader's ``last_index`` is a slice of."""
+        if self._arange is None:
+            self._arange = torch.arange(self.LR.shape[0], device=self.LR.device)
+        return self._arange
 
     def _virtual_len(self) -> int:
         n = self.LR.shape[0]
@@ -139,7 +166,11 @@ class DeviceSRLoader:
             lr = Fh.dihedral(self.LR, op, idx, axis_mode=self.axis_mode, op_mask=self._op_mask, tables=self._tables)
             if self._noise is not None:                                 # the virtual index: (sample, op) pairs differ under "expand"
                 Fh.taxel_noise(lr, self._noise, self.noise_seed, epoch, ids=order[lo:hi], out=lr)
-            yield lr, Fh.dihedral(self.HR, op, idx, op_mask=self._op_mask)
+            hr = Fh.dihedral(self.HR, op, idx, op_mask=self._op_mask)
+            if self.gamma is not None:
+                yield lr, hr, self.gamma.index_select(0, idx)
+            else:
+                yield lr, hr
 
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         if self._ops is not None:
@@ -162,4 +193,8 @@ class DeviceSRLoader:
                 lr, hr = self.LR.index_select(0, idx), self.HR.index_select(0, idx)
                 if self._noise is not None:
                     Fh.taxel_noise(lr, self._noise, self.noise_seed, epoch, ids=idx, out=lr)
-            yield lr, hr
+            if self.gamma is not None:
+                self.last_index = idx if order is not None else self._identity()[lo:hi]
+                yield lr, hr, (self.gamma.index_select(0, idx) if order is not None else self.gamma[lo:hi])
+            else:
+                yield lr, hr

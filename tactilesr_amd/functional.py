@@ -1,7 +1,8 @@
 """HIP-backed functional pieces of the SR training / eval step that sit outside the model:
 target preparation, MSE loss, PSNR / SSIM, the differentiable SSIM and the MSE + SSIM loss (reference
 train/tactileSR_train.py:41-51,66-101; utility/tools.py:49-114), and the pixel losses with a contact weight
-(L1 / Charbonnier / Huber: not in the reference, whose criterion is nn.MSELoss)."""
+(L1 / Charbonnier / Huber: not in the reference, whose criterion is nn.MSELoss), and the degradation-consistency term
+(the SR output pooled back onto the taxels by the sensor model's masks, model/tPSFNet.py:129-141)."""
 from __future__ import annotations
 
 import ctypes
@@ -191,54 +192,222 @@ def _plain_mse(pixel_kind, fg_weight) -> bool:
     return str(pixel_kind).lower() == "mse" and float(fg_weight) == 0
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# Degradation consistency (tsr_degrade_fwd_bwd, csrc/degrade_loss.hip): the image pooled onto the 4x4 taxels by the
+# sensor model's masks (reference model/tPSFNet.py:129-141 at 100x100), against the measured z-taxels.
+# ----------------------------------------------------------------------------------------------------------------------
+DEGRADE_MAX_HW = 128
+DEGRADE_MAX_WGS = 2048                                          # TSR_DEGRADE_MAX_WGS of include/tactilesr_hip.h
+DEGRADE_GAMMA_MAX = 1e6                                         # TSR_DEGRADE_GAMMA_MAX: beyond it the masks are flat
+
+
+def degrade_gamma_arg(gamma, B: int, device=None):
+    """``(gamma_dev tensor or None, gamma_all float)`` as ``tsr_degrade_fwd_bwd`` takes them: a float in (0, 1e6] for
+    every image, or a ``(B,)`` tensor on the device (made fp32 and contiguous; its values are checked by the kernel,
+    which answers a bad one with an all-NaN image).  ``TactileSRHipError`` otherwise.  Host-only for a float."""
+    if isinstance(gamma, torch.Tensor):
+        if gamma.dim() == 0 and not gamma.is_cuda:
+            gamma = float(gamma)
+        else:
+            if gamma.dim() != 1 or gamma.shape[0] != B:
+                raise TactileSRHipError(f"a gamma tensor must have shape ({B},), got {tuple(gamma.shape)}")
+            if device is not None and gamma.device != device:
+                raise TactileSRHipError(f"the gamma tensor is on {gamma.device}, the image on {device}")
+            return gamma.detach().float().contiguous(), 0.0
+    try:
+        g = float(gamma)
+    except (TypeError, ValueError) as e:
+        raise TactileSRHipError(f"degradation gamma: {e}") from None
+    if not (0 < g <= DEGRADE_GAMMA_MAX):
+        raise TactileSRHipError(f"the degradation gamma must be in (0, {DEGRADE_GAMMA_MAX:g}], got {g}")
+    return None, g
+
+
+def _degrade_gain(gain) -> float:
+    try:
+        g = float(gain)
+    except (TypeError, ValueError) as e:
+        raise TactileSRHipError(f"degradation gain: {e}") from None
+    if not _math.isfinite(g):
+        raise TactileSRHipError(f"the degradation gain must be finite, got {g}")
+    return g
+
+
+def _degrade_image(y: torch.Tensor, who: str) -> torch.Tensor:
+    if not y.is_cuda:
+        raise TactileSRHipError(f"{who} needs ROCm tensors (no CPU fallback)")
+    if y.dim() != 4 or y.shape[1] != 1 or not (1 <= y.shape[2] <= DEGRADE_MAX_HW and 1 <= y.shape[3] <= DEGRADE_MAX_HW):
+        raise TactileSRHipError(f"{who} needs a (B,1,H,W) image with 1 <= H, W <= {DEGRADE_MAX_HW}, got {tuple(y.shape)}")
+    return y.detach().float().contiguous()
+
+
+def _degrade_taxels(z: torch.Tensor, B: int, device, who: str):
+    """``(tensor to pass, z_bstride)`` of the taxels ``z`` -- (B,16), (B,4,4), (B,1,4,4) or a channel slice
+    ``LR[:, c]`` / ``LR[:, c:c+1]`` of a contiguous (B,C,4,4) fp32 tensor, which is passed in place."""
+    if z.device != device:
+        raise TactileSRHipError(f"{who}: the taxels are on {z.device}, the image on {device}")
+    if z.shape[0] != B or z.numel() != 16 * B:
+        raise TactileSRHipError(f"{who} needs 16 taxels per image, got {tuple(z.shape)} for {B} images")
+    z = z.detach()
+    zz = z.reshape(B, 16) if z.dim() == 2 else z.reshape(B, 4, 4) if z.shape[-2:] == (4, 4) else None
+    if zz is None:
+        raise TactileSRHipError(f"{who}: taxels of shape {tuple(z.shape)} are not (B,16) or (B,[1,]4,4)")
+    inner = (1,) if zz.dim() == 2 else (4, 1)
+    if zz.dtype == torch.float32 and tuple(zz.stride()[1:]) == inner and (B == 1 or zz.stride(0) >= 16):
+        return zz, (16 if B == 1 else zz.stride(0))
+    return zz.float().contiguous(), 16
+
+
+def _degrade_launch(y, z, z_bstride, gamma, gain, lr_deg, q, dy, dy_scale, accumulate, dz, max_wgs=None):
+    B, _, H, W = y.shape
+    gdev, gall = degrade_gamma_arg(gamma, B, y.device)
+    args = [ptr(y), _I(B), _I(H), _I(W), ctypes.c_void_p(z.data_ptr()) if z is not None else ptr(None), _L(z_bstride),
+            ptr(gdev), _D(gall), _D(_degrade_gain(gain)), ptr(lr_deg), ptr(q), ptr(dy), _F(dy_scale),
+            _I(1 if accumulate else 0), ptr(dz)]
+    if max_wgs is None:
+        call("tsr_degrade_fwd_bwd", *args, stream())
+    else:
+        call("tsr_degrade_fwd_bwd_wgs", *args, _I(int(max_wgs)), stream())
+
+
+def degrade(y: torch.Tensor, gamma, gain: float = 1.0) -> torch.Tensor:
+    """The sensor model's pooling of a (B,1,H,W) image onto the taxels, (B,1,4,4), no autograd: at 100x100 with
+    ``gain=1`` the reference's ``degradation_process`` (model/tPSFNet.py:129-141); on another grid the same masks
+    sampled at the pixel centres of ``F.interpolate(align_corners=False)``.  ``gamma`` (the mask width, ``alphaBeta[2]``)
+    is a float or a (B,) device tensor; ``gain`` multiplies the result (it undoes a ``/HR_scale_num`` of the image)."""
+    y = _degrade_image(y, "degrade")
+    out = torch.empty(y.shape[0], 1, 4, 4, dtype=torch.float32, device=y.device)
+    _degrade_launch(y, None, 0, gamma, gain, out, None, None, 0.0, False, None)
+    return out
+
+
+def degradation_fwd_bwd(y: torch.Tensor, z: torch.Tensor, gamma, gain: float = 1.0, dy=None, dy_scale: float = 1.0,
+                        accumulate: bool = False, want_dz: bool = False, want_dy: bool = True):
+    """``q_b = mean_ac (degrade(y)_b - z_b)^2`` per image and its gradients from one ``tsr_degrade_fwd_bwd`` launch,
+    outside autograd: ``(q (B,), lr_deg (B,1,4,4), dy)`` or, with ``want_dz``, ``(q, lr_deg, dy, dz (B,1,4,4))``.
+    ``dy = dy_scale * d q_b / d y`` is a new tensor, or the given contiguous fp32 ``dy`` written in place
+    (``accumulate=True``: added to it); ``dz = dy_scale * d q_b / d z``.  ``z`` is (B,16), (B,4,4), (B,1,4,4) or a channel
+    slice of a contiguous (B,C,4,4) fp32 tensor (read in place).  ``gamma`` is not differentiated.  ``want_dy=False``
+    (a score: ``eval_func``) passes no ``dy`` to the launch, which then neither allocates nor writes one, and returns
+    ``None`` in its place; the other outputs keep their bits."""
+    y = _degrade_image(y, "degradation_fwd_bwd")
+    B = y.shape[0]
+    zz, zs = _degrade_taxels(z, B, y.device, "degradation_fwd_bwd")
+    if not want_dy:
+        if dy is not None or accumulate:
+            raise TactileSRHipError("degradation_fwd_bwd: want_dy=False takes no dy and no accumulate")
+    elif dy is None:
+        if accumulate:
+            raise TactileSRHipError("degradation_fwd_bwd: accumulate=True needs the dy to add to")
+        dy = torch.empty_like(y)
+    elif dy.dtype != torch.float32 or dy.shape != y.shape or not dy.is_cuda or not dy.is_contiguous():
+        raise TactileSRHipError("degradation_fwd_bwd: dy must be a contiguous fp32 ROCm tensor of y's shape")
+    lr_deg = torch.empty(B, 1, 4, 4, dtype=torch.float32, device=y.device)
+    q = torch.empty(B, dtype=torch.float32, device=y.device)
+    dz = torch.empty(B, 1, 4, 4, dtype=torch.float32, device=y.device) if want_dz else None
+    _degrade_launch(y, zz, zs, gamma, gain, lr_deg, q, dy, dy_scale, accumulate, dz)
+    return (q, lr_deg, dy, dz) if want_dz else (q, lr_deg, dy)
+
+
+class _DegradationLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, z, gamma, gain):
+        want_dz = ctx.needs_input_grad[1]
+        res = degradation_fwd_bwd(y, z, gamma, gain, dy_scale=1.0 / y.shape[0], want_dz=want_dz)
+        ctx.save_for_backward(*res[2:])
+        ctx.z_shape = z.shape
+        return res[0].mean()
+
+    @staticmethod
+    def backward(ctx, gout):
+        saved = ctx.saved_tensors
+        dz = (saved[1] * gout).reshape(ctx.z_shape) if len(saved) == 2 else None
+        return saved[0] * gout, dz, None, None
+
+
+def degradation_loss(y: torch.Tensor, z: torch.Tensor, gamma, gain: float = 1.0) -> torch.Tensor:
+    """The autograd form of ``degradation_fwd_bwd``: ``mean_b q_b``, value and gradients from one launch.  ``y`` gets a
+    gradient, and so does ``z`` when it requires one; ``gamma`` never does."""
+    if not y.is_cuda or not z.is_cuda:
+        raise TactileSRHipError("degradation_loss needs ROCm tensors (no CPU fallback)")
+    if z.requires_grad and z.dtype != torch.float32:
+        raise TactileSRHipError("degradation_loss: taxels that require grad must be fp32")
+    return _DegradationLoss.apply(y.float(), z, gamma, gain)
+
+
 def sr_loss_fwd_bwd(y: torch.Tensor, target: torch.Tensor, ssim_weight: float = 0.0, data_range: float = 1.0,
                     window: int = 11, sigma: float = 1.5, K1: float = 0.01, K2: float = 0.03, return_parts: bool = False,
-                    pixel_kind: str = "mse", pixel_param=None, fg_weight: float = 0.0, fg_threshold: float = 0.0):
-    """``pixel(y, target) + ssim_weight * (1 - mean_b ssim_b)`` and its gradient w.r.t. ``y``, outside autograd:
-    ``(loss (1,), dy)``.  The pixel launch, then the SSIM launch accumulating ``-ssim_weight / B * d ssim_b / d y`` into
-    the same ``dy``.  The pixel term is the MSE launch (``mse_fwd_bwd``) for ``pixel_kind="mse"`` with ``fg_weight == 0``,
-    otherwise ``pixel_loss_fwd_bwd`` with the four pixel arguments; ``ssim_weight == 0`` is that launch alone, launch
-    for launch.  ``return_parts=True`` appends the two terms: ``(loss, dy, pixel (1,), ssim (B,) or None)``."""
+                    pixel_kind: str = "mse", pixel_param=None, fg_weight: float = 0.0, fg_threshold: float = 0.0,
+                    deg_weight: float = 0.0, deg_z=None, deg_gamma=None, deg_gain: float = 1.0):
+    """``pixel(y, target) + ssim_weight * (1 - mean_b ssim_b) + deg_weight * mean_b q_b`` and its gradient w.r.t. ``y``,
+    outside autograd: ``(loss (1,), dy)``.  The pixel launch, then the SSIM launch accumulating
+    ``-ssim_weight / B * d ssim_b / d y`` into the same ``dy``, then the degradation launch (``degradation_fwd_bwd`` on
+    the taxels ``deg_z`` with ``deg_gamma`` and ``deg_gain``) accumulating ``deg_weight / B * d q_b / d y``.  The pixel
+    term is the MSE launch (``mse_fwd_bwd``) for ``pixel_kind="mse"`` with ``fg_weight == 0``, otherwise
+    ``pixel_loss_fwd_bwd`` with the four pixel arguments; ``ssim_weight == 0`` and ``deg_weight == 0`` is that launch
+    alone, launch for launch, and ``deg_weight == 0`` issues exactly the launches it issued before the term existed.
+    ``return_parts=True`` appends the terms: ``(loss, dy, pixel (1,), ssim (B,) or None)`` and, with a non-zero
+    ``deg_weight``, ``q (B,)`` as a fifth."""
     if not y.is_cuda or not target.is_cuda:
         raise TactileSRHipError("sr_loss_fwd_bwd needs ROCm tensors (no CPU fallback)")
+    deg = float(deg_weight) != 0
+    if deg and (deg_z is None or deg_gamma is None):
+        raise TactileSRHipError("sr_loss_fwd_bwd: a non-zero deg_weight needs deg_z and deg_gamma")
     if _plain_mse(pixel_kind, fg_weight):
         mse, dy = mse_fwd_bwd(y, target)
     else:
         mse, dy = pixel_loss_fwd_bwd(y, target, pixel_kind, pixel_param, fg_weight, fg_threshold)
-    if ssim_weight == 0:
-        return (mse, dy, mse, None) if return_parts else (mse, dy)
-    t = target.detach().float().contiguous()
-    vals = _ssim_launch(y.contiguous(), t, data_range, window, sigma, K1, K2, dy, -float(ssim_weight) / y.shape[0], 1)
-    loss = mse + float(ssim_weight) * (1.0 - vals.mean())
-    return (loss, dy, mse, vals) if return_parts else (loss, dy)
+    loss, vals = mse, None
+    if ssim_weight != 0:
+        t = target.detach().float().contiguous()
+        vals = _ssim_launch(y.contiguous(), t, data_range, window, sigma, K1, K2, dy, -float(ssim_weight) / y.shape[0], 1)
+        loss = mse + float(ssim_weight) * (1.0 - vals.mean())
+    if not deg:
+        return (loss, dy, mse, vals) if return_parts else (loss, dy)
+    q = degradation_fwd_bwd(y, deg_z, deg_gamma, deg_gain, dy=dy, dy_scale=float(deg_weight) / y.shape[0],
+                            accumulate=True)[0]
+    loss = loss + float(deg_weight) * q.mean()
+    return (loss, dy, mse, vals, q) if return_parts else (loss, dy)
 
 
 class _SRLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, y, target, ssim_weight, data_range, window, sigma, pixel_kind, pixel_param, fg_weight, fg_threshold):
-        loss, dy, mse, vals = sr_loss_fwd_bwd(y, target, ssim_weight, data_range, window, sigma, return_parts=True,
-                                              pixel_kind=pixel_kind, pixel_param=pixel_param, fg_weight=fg_weight,
-                                              fg_threshold=fg_threshold)
+    def forward(ctx, y, target, ssim_weight, data_range, window, sigma, pixel_kind, pixel_param, fg_weight, fg_threshold,
+                deg_weight, deg_z, deg_gamma, deg_gain):
+        parts = sr_loss_fwd_bwd(y, target, ssim_weight, data_range, window, sigma, return_parts=True,
+                                pixel_kind=pixel_kind, pixel_param=pixel_param, fg_weight=fg_weight,
+                                fg_threshold=fg_threshold, deg_weight=deg_weight, deg_z=deg_z, deg_gamma=deg_gamma,
+                                deg_gain=deg_gain)
+        loss, dy, mse, vals = parts[:4]
         ctx.save_for_backward(dy)
         mse0 = mse[0]
+        if len(parts) == 5:
+            ctx.mark_non_differentiable(mse0, vals, parts[4]) if vals is not None else \
+                ctx.mark_non_differentiable(mse0, parts[4])
+            return loss[0], mse0, vals, parts[4]
         ctx.mark_non_differentiable(mse0, vals)
         return loss[0], mse0, vals
 
     @staticmethod
-    def backward(ctx, gout, _gmse, _gvals):
+    def backward(ctx, gout, *_gparts):
         (dy,) = ctx.saved_tensors
-        return (dy * gout,) + (None,) * 9
+        return (dy * gout,) + (None,) * 13
 
 
 def sr_loss(y: torch.Tensor, target: torch.Tensor, ssim_weight: float, data_range: float = 1.0, window: int = 11,
             sigma: float = 1.5, pixel_kind: str = "mse", pixel_param=None, fg_weight: float = 0.0,
-            fg_threshold: float = 0.0):
-    """The autograd form of ``sr_loss_fwd_bwd`` for ``ssim_weight != 0``: ``(loss, pixel term, per-sample ssim)``; only
-    ``loss`` carries a gradient (to ``y``)."""
+            fg_threshold: float = 0.0, deg_weight: float = 0.0, deg_z=None, deg_gamma=None, deg_gain: float = 1.0):
+    """The autograd form of ``sr_loss_fwd_bwd`` for a non-zero ``ssim_weight`` or ``deg_weight``:
+    ``(loss, pixel term, per-sample ssim)`` and, with a non-zero ``deg_weight``, the per-sample ``q`` as a fourth
+    (``ssim`` is then ``None`` when ``ssim_weight == 0``); only ``loss`` carries a gradient (to ``y`` -- the taxels
+    ``deg_z`` get none here: ``degradation_loss`` is the form that differentiates them)."""
     if not y.is_cuda:
         raise TactileSRHipError("sr_loss needs ROCm tensors (no CPU fallback)")
+    if float(deg_weight) != 0 and deg_z is None:
+        raise TactileSRHipError("sr_loss: a non-zero deg_weight needs deg_z and deg_gamma")
     return _SRLoss.apply(y.float(), target, float(ssim_weight), data_range, window, sigma, pixel_kind, pixel_param,
-                         fg_weight, fg_threshold)
+                         fg_weight, fg_threshold, float(deg_weight), None if deg_z is None else deg_z.detach(), deg_gamma,
+                         float(deg_gain))
 
 
 def psnr_ssim(a: torch.Tensor, b: torch.Tensor, maxValue: float, reference_quirk: bool = True,

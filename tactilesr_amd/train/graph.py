@@ -21,8 +21,10 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
   parameters that require grad (the captured backward holds only the launches a trainable parameter depends on), the set
   of BatchNorm layers in eval mode (``hold_bn_statistics``: their statistics launches are not in the capture), the loss
   config (the optional ``ssim_loss_weight`` / ``ssim_window`` / ``ssim_sigma`` / ``ssim_data_range`` and ``pixel_loss`` /
-  ``pixel_loss_param`` / ``contact_loss_weight`` / ``contact_threshold`` included: the captured loss is
-  ``functional.sr_loss_fwd_bwd``, the MSE or the configured pixel launch plus, for a non-zero weight, the SSIM launch),
+  ``pixel_loss_param`` / ``contact_loss_weight`` / ``contact_threshold`` and ``degradation_loss_weight`` /
+  ``degradation_gamma`` / ``degradation_channel`` / ``degradation_gain`` included: the captured loss is
+  ``functional.sr_loss_fwd_bwd``, the MSE or the configured pixel launch plus, for a non-zero weight, the SSIM launch
+  and, for a non-zero degradation weight, the degradation launch on a channel slice of the static ``LR``),
   the optimizer's baked constants (``betas``, ``eps``, ``weight_decay``) or ``clip_grad_norm`` change, the graph is dropped and the next ``warmup`` calls run eagerly again before a new capture.  ``captures`` counts the captures.
 * The returned ``total_loss`` is the graph's static OUTPUT BUFFER (like ``GraphedForward``): the next call overwrites
   it, so clone it to keep it.  It carries no autograd graph.
@@ -48,6 +50,8 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
   a static one-float device buffer before that replay.  The shadow is then the eager step's bit for bit.  The identity of
   ``e``, its shadow address and its ``buffers`` mode are baked in: another or a re-allocated EMA recaptures.  ``ema=None``
   (the default) captures the step as before.
+* Per-sample gamma: a batch may be ``(LR, HR_raw, gamma)`` with ``gamma`` (B,) fp32; it is copied into a third static
+  buffer that the captured degradation launch reads, and its shape joins the batch signature.
 * Refused (``TactileSRHipError``): eval mode, a batch whose shape / dtype differs from the first call's, an attached
   ``GradSync`` (no collectives inside a graph), ``engine.profile`` / ``engine.debug`` / ``engine.keep_ctx``, an
   optimizer other than ``tactilesr_amd.optim.Adam``, a model not on a ROCm device, a model without a trainable
@@ -62,7 +66,8 @@ from .. import functional as Fh
 from .. import optim as opt_mod
 from .._lib import TactileSRHipError
 from ..ddp import note_forward
-from .tactileSR_train import _prep, pixel_is_plain_mse, pixel_loss_config, ssim_loss_config, train_one_iter
+from .tactileSR_train import (_batch_gamma, _degradation_gamma, _prep, degradation_loss_config, pixel_is_plain_mse,
+                              pixel_loss_config, ssim_loss_config, train_one_iter)
 
 _CONFIG_KEYS = ("HR_scale_num", "scale_factor", "seqsCnt", "axisCnt")      # what the captured train_cal_loss bakes in
 
@@ -92,7 +97,7 @@ class GraphedTrainStep:
 
     def _drop(self) -> None:
         self.graph = None
-        self._out = self._launches = self._hyper = self._LR = self._HR = None
+        self._out = self._launches = self._hyper = self._LR = self._HR = self._G = None
         self._norm = self._norm_work = self._norm_table = None
         self._ema_omd = self._ema_table = None
         self._graph_key = None
@@ -110,22 +115,24 @@ class GraphedTrainStep:
         return (m.train_impl, id(arena), arena.flat.data_ptr() if arena is not None else 0,
                 tuple(t.data_ptr() for t in m.parameters()), tuple(b.data_ptr() for b in m.buffers()), groups,
                 tuple(self.config[k] for k in _CONFIG_KEYS), ssim_loss_config(self.config), pixel_loss_config(self.config),
-                self.clip_grad_norm,
+                degradation_loss_config(self.config), self.clip_grad_norm,
                 (id(self.ema), self.ema._flat.data_ptr(), self.ema.buffers) if self.ema is not None else None,
                 tuple(p.requires_grad for p in m.parameters()),      # the captured backward holds the trainable set's launches
                 tuple(mod.training for mod in m.modules() if isinstance(mod, torch.nn.BatchNorm2d)))      # and each BatchNorm's mode
 
-    def _check(self, LR, HR) -> None:
+    def _check(self, LR, HR, gamma=None) -> None:
         m = self.model
         if not m.training:
             raise TactileSRHipError("GraphedTrainStep replays the TRAIN step: the model is in eval mode")
         if not any(p.requires_grad for p in m.parameters()):
             raise TactileSRHipError("GraphedTrainStep: no model parameter requires grad (nothing to train)")
         sig = (tuple(LR.shape), LR.dtype, tuple(HR.shape), HR.dtype)
+        if gamma is not None:                    # a 3-tuple batch: the per-sample gamma is a third static input
+            sig += (tuple(gamma.shape), gamma.dtype)
         if self._sig is None:
             self._sig = sig
         elif sig != self._sig:
-            raise TactileSRHipError(f"GraphedTrainStep was set up for batch (LR, HR_raw) of shape / dtype {self._sig}, "
+            raise TactileSRHipError(f"GraphedTrainStep was set up for batch (LR, HR_raw[, gamma]) of shape / dtype {self._sig}, "
                                     f"got {sig}")
         eng = m.train_engine()
         if eng.grad_sync is not None:
@@ -142,10 +149,14 @@ class GraphedTrainStep:
                                         "optimizer (the norm is taken over model.parameters(), the fused clip over "
                                         "the optimizer's)")
 
-    def _capture(self, LR, HR) -> None:
+    def _capture(self, LR, HR, gamma=None) -> None:
         m, opt = self.model, self.optimizer
         dev = next(m.parameters()).device
         pixel = pixel_loss_config(self.config)     # refuses a bad key before anything is captured
+        deg = degradation_loss_config(self.config)
+        if gamma is not None:
+            self._G = torch.empty(gamma.shape, dtype=torch.float32, device=dev)
+        deg_gamma = _degradation_gamma(deg, self._G) if deg[0] != 0 else None
         self._LR = torch.empty(LR.shape, dtype=LR.dtype, device=dev)
         self._HR = torch.empty(HR.shape, dtype=HR.dtype, device=dev)
         # one row of {lr, bc1, bc2_sqrt} ({lr, bc1, bc2_sqrt, decay}: AdamW, AMSGrad) per Adam launch; at most one
@@ -176,9 +187,17 @@ class GraphedTrainStep:
                 note_forward(eng, ctx)
             weight, window, sigma, data_range = ssim_loss_config(self.config)
             kind, param, fg_weight, fg_threshold = pixel
-            loss, dy, pix, vals = Fh.sr_loss_fwd_bwd(out.float(), HR, weight, data_range, window, sigma,
-                                                     return_parts=True, pixel_kind=kind, pixel_param=param,
-                                                     fg_weight=fg_weight, fg_threshold=fg_threshold)
+            if deg[0] == 0:
+                loss, dy, pix, vals = Fh.sr_loss_fwd_bwd(out.float(), HR, weight, data_range, window, sigma,
+                                                         return_parts=True, pixel_kind=kind, pixel_param=param,
+                                                         fg_weight=fg_weight, fg_threshold=fg_threshold)
+            else:                                # the z-taxels are a slice of the static LR, read in place
+                loss, dy, pix, vals, q = Fh.sr_loss_fwd_bwd(out.float(), HR, weight, data_range, window, sigma,
+                                                            return_parts=True, pixel_kind=kind, pixel_param=param,
+                                                            fg_weight=fg_weight, fg_threshold=fg_threshold,
+                                                            deg_weight=deg[0], deg_z=LR[:, deg[2]], deg_gamma=deg_gamma,
+                                                            deg_gain=deg[3])
+                deg_mean = q.mean()
             # weight 0: the pixel launch alone; the plain MSE: mse_fwd_bwd
             ssim_mean = vals.mean() if vals is not None else None
             opt.zero_grad()
@@ -197,7 +216,11 @@ class GraphedTrainStep:
         # the launches (and the norm launch) hold the Adam chunk tables the graph reads: keep them alive with it
         out_dict = {"total_loss": loss[0]}
         pix_key = "mse_loss" if pixel_is_plain_mse(pixel) else "pixel_loss"
-        if vals is not None:                     # train_cal_loss's loss_dict with an SSIM term
+        if deg[0] != 0:                          # train_cal_loss's loss_dict with a degradation term
+            out_dict.update({pix_key: pix[0], "degradation_loss": deg_mean})
+            if vals is not None:
+                out_dict["ssim"] = ssim_mean
+        elif vals is not None:                   # with an SSIM term
             out_dict.update({pix_key: pix[0], "ssim": ssim_mean})
         elif pix_key == "pixel_loss":            # and with a configured pixel criterion alone
             out_dict["pixel_loss"] = loss[0]
@@ -208,8 +231,9 @@ class GraphedTrainStep:
         self.captures += 1
 
     def __call__(self, batch):
-        LR, HR = batch
-        self._check(LR, HR)
+        LR, HR = batch[0], batch[1]
+        gamma = _batch_gamma(batch, LR.device)
+        self._check(LR, HR, gamma)
         if self.graph is not None and self._key() != self._graph_key:
             self._drop()
         if self.graph is None and self._eager_left > 0:
@@ -217,9 +241,11 @@ class GraphedTrainStep:
             return train_one_iter(self.model, self.optimizer, batch, self.config, clip_grad_norm=self.clip_grad_norm,
                                   ema=self.ema)
         if self.graph is None:
-            self._capture(LR, HR)
+            self._capture(LR, HR, gamma)
         self._LR.copy_(LR)
         self._HR.copy_(HR)
+        if gamma is not None:
+            self._G.copy_(gamma)
         rows = self.optimizer._replay_rows(self._launches)       # advances state["step"]; a fresh pinned tensor
         if self._norm_table is not None:
             self.optimizer.launches += opt_mod.GN_LAUNCHES

@@ -10,9 +10,12 @@ path needs from it are the three functions below with the same argument meaning:
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from .. import functional as Fh
+from .._lib import TactileSRHipError
 
 
 def default_config():
@@ -22,11 +25,23 @@ def default_config():
 
 
 def _prep(batch, config, device):
-    LR, HR = batch
+    LR, HR = batch[0], batch[1]          # a third element (the per-sample gamma) is read by _batch_gamma
     LR, HR = LR.to(device), HR.to(device)
     HR = Fh.prepare_target(HR, config["HR_scale_num"], config["scale_factor"])
     LR = LR.type(torch.float32)[:, :config["seqsCnt"] * config["axisCnt"]]
     return LR, HR
+
+
+def _batch_gamma(batch, device):
+    """The (B,) fp32 per-sample gamma of a 3-tuple batch ``(LR, HR, gamma)`` on ``device``, ``None`` for a 2-tuple."""
+    if len(batch) == 2:
+        return None
+    if len(batch) != 3:
+        raise TactileSRHipError(f"a batch is (LR, HR) or (LR, HR, gamma), got {len(batch)} elements")
+    g = batch[2]
+    if not isinstance(g, torch.Tensor) or g.dim() != 1 or g.shape[0] != batch[0].shape[0]:
+        raise TactileSRHipError("the third element of a batch is the per-sample gamma, a (B,) tensor")
+    return g.to(device).float()
 
 
 def ssim_loss_config(config):
@@ -50,6 +65,55 @@ def pixel_loss_config(config):
                               config.get("contact_loss_weight", 0.0), config.get("contact_threshold", 0.0))
 
 
+def degradation_loss_config(config):
+    """The optional degradation-consistency keys, returned as ``(weight, gamma, channel, gain)``:
+
+    * ``degradation_loss_weight`` (default 0: off) -- the weight of ``mean_b q_b``, ``q_b`` the mean squared difference
+      between the SR output pooled onto the taxels by the sensor model (``functional.degrade``) and the z-taxels the
+      output was computed from;
+    * ``degradation_gamma`` -- the mask width, a float in (0, 1e6], for every sample; ``None`` when absent: a non-zero weight
+      then needs a batch that carries its own ``gamma`` (a 3-tuple), which also overrides this key;
+    * ``degradation_channel`` (default ``axisCnt - 1``, the z axis of the first frame) -- the channel of the prepared
+      ``LR`` that holds the z-taxels;
+    * ``degradation_gain`` (default ``HR_scale_num``) -- undoes the ``/HR_scale_num`` of the prepared target.
+
+    With weight 0 the other keys are not read.  A bad value raises ``TactileSRHipError`` here, before any launch."""
+    try:
+        w = float(config.get("degradation_loss_weight", 0.0))
+    except (TypeError, ValueError) as e:
+        raise TactileSRHipError(f"degradation_loss_weight: {e}") from None
+    if not math.isfinite(w):
+        raise TactileSRHipError(f"degradation_loss_weight must be finite, got {w}")
+    if w == 0:
+        return 0.0, None, None, None
+    gamma = config.get("degradation_gamma", None)
+    if gamma is not None:
+        if isinstance(gamma, torch.Tensor):
+            raise TactileSRHipError("degradation_gamma is a float; a per-sample gamma travels with the batch")
+        gamma = Fh.degrade_gamma_arg(gamma, 0)[1]
+    n_ch = int(config["seqsCnt"]) * int(config["axisCnt"])
+    ch = config.get("degradation_channel", int(config["axisCnt"]) - 1)
+    if isinstance(ch, bool) or not isinstance(ch, int) or not 0 <= ch < n_ch:
+        raise TactileSRHipError(f"degradation_channel must be an int in [0, {n_ch}), got {ch!r}")
+    try:
+        gain = float(config.get("degradation_gain", config["HR_scale_num"]))
+    except (TypeError, ValueError) as e:
+        raise TactileSRHipError(f"degradation_gain: {e}") from None
+    if not math.isfinite(gain):
+        raise TactileSRHipError(f"degradation_gain must be finite, got {gain}")
+    return w, gamma, ch, gain
+
+
+def _degradation_gamma(deg, batch_gamma):
+    """The gamma the launch takes: the batch's own, else the config scalar; refused when a non-zero weight has neither."""
+    if batch_gamma is not None:
+        return batch_gamma
+    if deg[1] is None:
+        raise TactileSRHipError("degradation_loss_weight is non-zero but there is no degradation_gamma key and the batch "
+                                "carries no gamma")
+    return deg[1]
+
+
 def pixel_is_plain_mse(pixel) -> bool:
     """Whether a ``pixel_loss_config`` result is the reference's criterion: the step then issues the MSE launch."""
     return pixel[0] == "mse" and pixel[2] == 0
@@ -57,13 +121,30 @@ def pixel_is_plain_mse(pixel) -> bool:
 
 def train_cal_loss(model, batch, config):
     """``total_loss`` is always in the dict.  With an SSIM term it also holds ``ssim`` and the pixel term, under
-    ``mse_loss`` when that is the plain MSE; under any other pixel setting the term is reported as ``pixel_loss``."""
+    ``mse_loss`` when that is the plain MSE; under any other pixel setting the term is reported as ``pixel_loss``.
+
+    With a non-zero ``degradation_loss_weight`` (``degradation_loss_config``) the loss gains
+    ``weight * mean_b q_b`` and the dict ``degradation_loss`` (that mean) and the pixel term under its usual key.  The
+    z-taxels are the prepared ``LR[:, degradation_channel]``, detached: the term sends no gradient to ``LR``
+    (``LR.grad`` holds what the pixel and SSIM terms send through the model, nothing from the residual's own
+    ``d q / d z``).  A batch may be ``(LR, HR, gamma)`` with a (B,) per-sample ``gamma``, which overrides
+    ``degradation_gamma``; without the key, or with weight 0, the step is unchanged."""
     device = next(model.parameters()).device
     pixel = pixel_loss_config(config)
+    deg = degradation_loss_config(config)
+    gamma = _degradation_gamma(deg, _batch_gamma(batch, device)) if deg[0] != 0 else None
     LR, HR = _prep(batch, config, device)
     out = model(LR)
     weight, window, sigma, data_range = ssim_loss_config(config)
     plain = pixel_is_plain_mse(pixel)
+    if deg[0] != 0:
+        res = Fh.sr_loss(out, HR, weight, data_range, window, sigma, *pixel, deg_weight=deg[0],
+                         deg_z=LR.detach()[:, deg[2]], deg_gamma=gamma, deg_gain=deg[3])
+        loss, pix, vals, q = res
+        d = {"total_loss": loss, "mse_loss" if plain else "pixel_loss": pix, "degradation_loss": q.mean()}
+        if vals is not None:
+            d["ssim"] = vals.mean()
+        return loss, d
     if weight == 0:
         if plain:
             loss = Fh.mse_loss(out, HR)
@@ -131,7 +212,7 @@ def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite
 
 @torch.no_grad()
 def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=None, ema=None, taxel_noise=None,
-              noise_seed=0):
+              noise_seed=0, degradation=False):
     """The reference's three averages (loss, SSIM, PSNR).  ``windowed_ssim=True`` appends a fourth: the windowed SSIM
     of ``functional.ssim`` with the config's ``ssim_window`` / ``ssim_sigma`` / ``ssim_data_range`` (``ssim_loss_config``),
     averaged the same way; the first three are unchanged.
@@ -147,10 +228,19 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
     scores the model on degraded taxels: after ``_prep`` each batch's ``LR`` passes through one
     ``functional.taxel_noise`` launch with seed ``noise_seed``, offset 0 and ``id_base`` = the number of samples seen so
     far, so sample ``k`` of the set always meets the same noise -- the score is deterministic and does not depend on the
-    loader's batch size (beyond the averaging over batches itself).  It composes with ``self_ensemble`` and ``ema``."""
+    loader's batch size (beyond the averaging over batches itself).  It composes with ``self_ensemble`` and ``ema``.
+
+    ``degradation=True`` (default ``False``: the results unchanged) appends one more value, after the windowed SSIM when
+    that is on: the batch-averaged ``mean_b q_b`` of ``functional.degradation_fwd_bwd`` between the output pooled onto
+    the taxels and the (noisy, when ``taxel_noise`` is on) z-taxels the model saw -- a score that needs no HR.  It reads
+    ``degradation_gamma`` / ``degradation_channel`` / ``degradation_gain`` of ``degradation_loss_config`` whatever the
+    weight; a 3-tuple batch's per-sample ``gamma`` overrides the key."""
     if ema is not None:
         with ema.applied():
-            return eval_func(model, test_loader, config, windowed_ssim, self_ensemble, None, taxel_noise, noise_seed)
+            return eval_func(model, test_loader, config, windowed_ssim, self_ensemble, None, taxel_noise, noise_seed,
+                             degradation)
+    deg = degradation_loss_config({**config, "degradation_loss_weight": 1.0}) if degradation else None
+    tot_deg = 0.0
     noise = Fh.taxel_noise_spec(taxel_noise)
     seen = 0
     device = next(model.parameters()).device
@@ -170,7 +260,13 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
         tot_ssim += float(ss.mean())
         if windowed_ssim:
             tot_wssim += float(Fh.ssim(out, HR, data_range, window, sigma).mean())
+        if degradation:
+            gamma = _degradation_gamma(deg, _batch_gamma(batch, device))
+            tot_deg += float(Fh.degradation_fwd_bwd(out, LR[:, deg[2]], gamma, deg[3], want_dy=False)[0].mean())
         n += 1
+    res = (tot_loss / n, tot_ssim / n, tot_psnr / n)
     if windowed_ssim:
-        return tot_loss / n, tot_ssim / n, tot_psnr / n, tot_wssim / n
-    return tot_loss / n, tot_ssim / n, tot_psnr / n
+        res += (tot_wssim / n,)
+    if degradation:
+        res += (tot_deg / n,)
+    return res

@@ -18,7 +18,15 @@ steps run at the reference's warm-up start learning rate, and a case whose outpu
 times the pixel-loss launch (tsr_pixel_loss_fwd_bwd) instead, at B = 32 and B = 8192 of 1x40x40, in one process: the
 launch pair at every kind without and with a contact weight (and with the target gradient), the MSE launch pair
 (tsr_mse_fwd_bwd) beside it, both on preallocated buffers, and the same loss with its gradient composed from torch ops
-through autograd, the contact mask included.  Sparse contact targets, predictions relu(t + noise)."""
+through autograd, the contact mask included.  Sparse contact targets, predictions relu(t + noise).
+
+    python tools/loss_microbench.py --degradation [--rounds R] [--out profiles/degradation_loss_cost.json]
+times the degradation-consistency launch (tsr_degrade_fwd_bwd) instead, in one process: the launch on preallocated
+buffers at B = 32 and B = 8192 of 1x40x40 and 1x100x100 -- the forward alone, and with q and an accumulating dy as the
+train step calls it -- against the same term and its gradient composed from torch ops in fp32 through autograd (the mask
+tables prepared once outside the timing; per call two batched matmuls, the mask floor, the residual and the MSE); and
+the B = 32 train step, eager and graph-replayed, without the key (the step as it was before the term existed) and with
+``degradation_loss_weight`` 0.1."""
 import argparse
 import json
 import os
@@ -187,6 +195,110 @@ def pixel_cases(a):
     return cases
 
 
+DEG_SHAPES = ((32, 40, 40), (8192, 40, 40), (32, 100, 100), (8192, 100, 100))
+DEG_GAMMA, DEG_GAIN = 0.7, 10.0
+
+
+def torch_degrade_tables(H, W, gamma, device):
+    """(E (4,H), F (4,W), mn, k / gain) in fp32 for `torch_degrade`, evaluated in fp64."""
+    KM = 100.0 / 15138.0
+    c = 12.0 + 25.0 * torch.arange(4, dtype=torch.float64).view(4, 1)
+    tab = [torch.exp(-KM * ((torch.arange(n, dtype=torch.float64) + 0.5) * 100.0 / n - 0.5 - c) ** 2 / gamma) for n in (H, W)]
+    mn = float(torch.exp(torch.tensor(-100.0 / gamma, dtype=torch.float64)))
+    return tab[0].float().to(device), tab[1].float().to(device), mn, 1e-4 * (100.0 / H) * (100.0 / W) / (1 - mn)
+
+
+def torch_degrade(y, z, tables, gain):
+    """mean_b q_b and its gradient with respect to y from torch ops through autograd (the eager alternative)."""
+    E, F, mn, k = tables
+    yy = y.detach().requires_grad_(True)
+    S = torch.matmul(torch.matmul(E, yy[:, 0]), F.t())                               # (B,4,4): two batched matmuls
+    D = (gain * k) * (S - mn * yy.sum(dim=(1, 2, 3)).view(-1, 1, 1))
+    loss = ((D - z) ** 2).mean()
+    return loss, torch.autograd.grad(loss, yy)[0]
+
+
+def degradation_cases(a):
+    from tactilesr_amd import _lib
+    from tactilesr_amd._lib import c_double, c_float, c_int, c_longlong, ptr, stream
+    cases = []
+    for B, H, W in DEG_SHAPES:
+        gen = torch.Generator().manual_seed(43)
+        y = blobs(B, H, W, gen, amp=1.0).cuda()
+        z = (torch.rand(B, 3, 4, 4, generator=gen) * 8).cuda()
+        zc = z[:, 2]                                                # a channel slice, read in place
+        zt = zc.contiguous()
+        dy, lr_deg, q = torch.zeros_like(y), torch.empty(B, 16, device="cuda"), torch.empty(B, device="cuda")
+        tables = torch_degrade_tables(H, W, DEG_GAMMA, "cuda")
+
+        def launch(with_z, with_dy):
+            _lib.call("tsr_degrade_fwd_bwd", ptr(y), c_int(B), c_int(H), c_int(W),
+                      _lib.c_void_p(zc.data_ptr() if with_z else 0), c_longlong(48), ptr(None), c_double(DEG_GAMMA),
+                      c_double(DEG_GAIN), ptr(lr_deg), ptr(q if with_z else None), ptr(dy if with_dy else None),
+                      c_float(WEIGHT / B), c_int(1 if with_dy else 0), ptr(None), stream())
+
+        fns = {"degrade_forward": lambda: launch(False, False), "degrade_q": lambda: launch(True, False),
+               "degrade_q_dy": lambda: launch(True, True),
+               "functional_fwd_bwd": lambda: Fh.degradation_fwd_bwd(y, zc, DEG_GAMMA, DEG_GAIN, dy=dy, dy_scale=WEIGHT / B,
+                                                                    accumulate=True),
+               "torch_fwd_bwd": lambda: torch_degrade(y, zt, tables, DEG_GAIN)}
+        px = B * H * W * 4
+        moved = {"degrade_forward": px, "degrade_q": px, "degrade_q_dy": 3 * px}     # y read; dy read and written
+        rounds = alternate(fns, a.warmup, a.rounds, a.launches if B <= 32 else max(a.launches // 5, 5))
+        med = {k: statistics.median(v) for k, v in rounds.items()}
+        for k, v in rounds.items():
+            case = dict(shape=[B, 1, H, W], launch=k, ms_median=round(med[k], 5), ms_spread=round(max(v) - min(v), 5),
+                        rounds_ms=[round(x, 5) for x in v], ratio_to_torch=round(med[k] / med["torch_fwd_bwd"], 4))
+            if k in moved:
+                case.update(bytes_moved=moved[k], gb_per_s=round(moved[k] / med[k] / 1e6, 1))
+            cases.append(case)
+            print(f"[loss microbench] degradation ({B},1,{H},{W}) {k:19s}: {med[k]:8.4f} ms (spread {case['ms_spread']:.4f}), "
+                  f"{case['ratio_to_torch']:.3f} x the torch composition" +
+                  (f", {case['gb_per_s']:.0f} GB/s" if k in moved else ""), flush=True)
+        del y, dy
+        torch.cuda.empty_cache()
+    return cases
+
+
+def degradation_step_cases(a):
+    """The B = 32 train step, eager and graph-replayed: without the key (the step as it was) and with weight 0.1."""
+    cases = []
+    B = 32
+    gen = torch.Generator().manual_seed(43)
+    batch = ((torch.rand(B, 3, 4, 4, generator=gen) * 8).cuda(), (blobs(B, 100, 100, gen) * 10).cuda())
+    for mode in ("eager", "graphed"):
+        fns, models = {}, {}
+        for name in ("no_key", f"weight_{WEIGHT}"):
+            m, opt, conf = build(None)
+            if name != "no_key":
+                conf.update(degradation_loss_weight=WEIGHT, degradation_gamma=DEG_GAMMA)
+            models[name] = m
+            if mode == "graphed":
+                fns[name] = lambda g=GraphedTrainStep(m, opt, conf, warmup=1): g(batch)
+            else:
+                fns[name] = lambda m=m, opt=opt, conf=conf: TR.train_one_iter(m, opt, batch, conf)
+        n = a.steps * 10
+        rounds = alternate(fns, max(a.warmup, 3), a.rounds, n)
+        med = {k: statistics.median(v) for k, v in rounds.items()}
+        run_spread = max(max(v) - min(v) for v in rounds.values())
+        for name, v in rounds.items():
+            with torch.no_grad():
+                models[name].eval()
+                frac = float((models[name](batch[0][:8].float()) > 0).float().mean())
+                models[name].train()
+            case = dict(B=B, mode=mode, loss=name, ms_per_step_median=round(med[name], 4),
+                        ms_per_step_spread=round(max(v) - min(v), 4), rounds_ms=[round(x, 4) for x in v],
+                        delta_to_no_key_ms=round(med[name] - med["no_key"], 4), run_spread_ms=round(run_spread, 4),
+                        steps_per_round=n, out_nonzero_frac=round(frac, 5), valid=bool(frac > 0))
+            cases.append(case)
+            print(f"[loss microbench] degradation step B={B} {mode:7s} {name:10s}: {med[name]:9.4f} ms/step (spread "
+                  f"{case['ms_per_step_spread']:.4f}), {case['delta_to_no_key_ms']:+.4f} ms to no key (run spread "
+                  f"{run_spread:.4f})" + ("" if case["valid"] else "  INVALID: the output is all zero"), flush=True)
+        del fns, models
+        torch.cuda.empty_cache()
+    return cases
+
+
 def build(weight):
     torch.manual_seed(42)
     m = tactilesr_amd.TactileSR().cuda().train()
@@ -262,16 +374,23 @@ def main():
     ap.add_argument("--steps-of", choices=("b2048_eager", "b32_eager", "b32_graphed"), default=None,
                     help="time only this step comparison")
     ap.add_argument("--pixel-loss", action="store_true", help="time the pixel-loss launch instead (see the docstring)")
-    ap.add_argument("--out", default=None, help="default: profiles/ssim_loss_cost.json, or profiles/pixel_loss_cost.json "
-                                                "with --pixel-loss")
+    ap.add_argument("--degradation", action="store_true", help="time the degradation launch and its step instead (see "
+                                                               "the docstring)")
+    ap.add_argument("--out", default=None, help="default: profiles/ssim_loss_cost.json, profiles/pixel_loss_cost.json "
+                                                "with --pixel-loss, profiles/degradation_loss_cost.json with --degradation")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "pixel_loss_cost.json" if a.pixel_loss else "ssim_loss_cost.json")
+        a.out = os.path.join(REPO, "profiles", "degradation_loss_cost.json" if a.degradation else
+                             "pixel_loss_cost.json" if a.pixel_loss else "ssim_loss_cost.json")
     if not torch.cuda.is_available():
         raise SystemExit("loss_microbench: needs a ROCm device (the timing is of the GPU)")
     result = dict(tool="tools/loss_microbench.py", device=torch.cuda.get_device_name(0), rounds=a.rounds, warmup=a.warmup,
                   launches=a.launches, steps=a.steps, weight=WEIGHT, lr=LR_START)
-    if a.pixel_loss:
+    if a.degradation:
+        result = dict(tool="tools/loss_microbench.py --degradation", device=result["device"], rounds=a.rounds,
+                      warmup=a.warmup, launches=a.launches, steps=a.steps, weight=WEIGHT, gamma=DEG_GAMMA, gain=DEG_GAIN,
+                      lr=LR_START, launch=degradation_cases(a), step=degradation_step_cases(a))
+    elif a.pixel_loss:
         result = dict(tool="tools/loss_microbench.py --pixel-loss", device=result["device"], rounds=a.rounds,
                       warmup=a.warmup, launches=a.launches, contact_weight=CONTACT[0], contact_threshold=CONTACT[1],
                       pixel=pixel_cases(a))
