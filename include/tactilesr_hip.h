@@ -696,6 +696,55 @@ int tsr_degrade_fwd_bwd_wgs(const float* y, int B, int H, int W, const float* z,
                             const float* gamma_dev, double gamma_all, double gain, float* lr_deg, float* q, float* dy,
                             float dy_scale, int accumulate, float* dz, int max_wgs, void* stream);
 
+/* Per-sample supervision weights (csrc/sample_weight.hip, csrc/pixel_loss.hip, csrc/ssim_loss.hip): every image b of a
+ * batch of B carries a weight w_b >= 0 with which the pixel and SSIM terms count it; w_b = 0 is an unlabeled image whose
+ * target is never read.  With P = H W pixels per image, omega_p = 1 + fg_weight [t_p > fg_threshold], rho and d_p as in
+ * tsr_pixel_loss_fwd_bwd, ssim_b as in tsr_ssim_fwd_bwd and q_b as in tsr_degrade_fwd_bwd (which takes no weight):
+ *   pix_b = (1/P) sum_p omega_p rho(d_p)
+ *   L     = (1/B) sum_{s_b != 0} s_b [pix_b + ls (1 - ssim_b)]  +  ld (1/B) sum_b q_b
+ *   dL/dy_bp = (s_b/B) [omega_p rho'(d_p)/P - ls d ssim_b/d y_bp]  +  (ld/B) d q_b/d y_bp
+ * A weight is VALID when it is finite and >= 0 (-0 is 0).  The scale s_b of tsr_sample_scale:
+ *   mode 0 ("sum")    D = sum of the valid w_b, fp64, in index order;  s_b = fl32(w_b B / D), or 0 when D == 0: the
+ *                     supervised terms are means over the labeled weight; uniform weights give s_b = 1 exactly
+ *   mode 1 ("batch")  s_b = w_b: the divisor stays B
+ *   an invalid w_b    s_b = NaN, and w_b is left out of D: that image's terms are NaN, no other image's are
+ * stats[0] = fl32(D), stats[1] = the number of valid w_b > 0 (both modes).  One workgroup.  s must not alias w.
+ * A SKIPPED image is one whose s_b == 0 exactly: its y and t are not read, its entry of a value vector (pix, ssim) is
+ * written as 0, its dy rows are 0 on overwrite and untouched on accumulate, its dt rows are 0.
+ *
+ * tsr_pixel_loss_ps_fwd_bwd is the per-image form of tsr_pixel_loss_fwd_bwd for y, t (B,P) fp32 contiguous:
+ * pix (B) receives pix_b, the image's own mean (NOT multiplied by s_b).  A gradient element is the fp64 value
+ * tsr_pixel_loss_fwd_bwd rounds for n = B P (dy_scale omega_p rho'(d_p) / (B P)), multiplied last by (double)s_b and
+ * rounded once: with s NULL (all ones) or s_b == 1, dy and dt equal the flat launch's bit for bit.  dy (optional) and dt
+ * (optional, always overwritten, dt != dy) follow the flat launch's contract.  One workgroup per image, at most max_wgs
+ * (TSR_PIXEL_LOSS_PS_MAX_WGS without the _wgs suffix) of them walking the batch at a stride of the grid; the image's sum
+ * is fp64 in a fixed order that depends on P alone (thread k of 256 owns elements 4j .. 4j+3 for j = k, k + 256, ...;
+ * then the flat launch's workgroup sum); no atomics, no work buffer: neither the cap nor a second launch changes a bit.
+ * 16-byte accesses when P % 4 == 0 and y, t and the given dy, dt are 16-byte aligned; otherwise the same elements move one
+ * float at a time with the same bits.  1 <= P <= 2^28.  Non-finite pixels stay in their own element and their own pix_b;
+ * a NaN s_b makes its image's whole dy and dt NaN.
+ * Refusals (status 1 before any device call, nothing written): those of tsr_pixel_loss_fwd_bwd (loss and work aside); B <= 0;
+ * P <= 0 or above 2^28; a NULL pix; max_wgs < 1.
+ *
+ * tsr_ssim_fwd_bwd_ps is tsr_ssim_fwd_bwd with s (B), NULL = all ones: the gradient factor is
+ * (double)dy_scale (double)s_b; ssim_b is the image's own value; a skipped image does no window work.  With s NULL or all
+ * ones the bits are those of tsr_ssim_fwd_bwd.  Refusals: those of tsr_ssim_fwd_bwd.
+ *
+ * tsr_weighted_mean: out[0] = fl32((1/B) sum_{s_b != 0} s_b v_b), fp64, in index order; s NULL = the plain mean.  v_b is
+ * not read where s_b == 0 (a NaN there never reaches out).  One workgroup.
+ * Refusals: tsr_sample_scale a NULL w, s or stats, B <= 0, mode outside {0, 1}; tsr_weighted_mean a NULL v or out, B <= 0. */
+#define TSR_PIXEL_LOSS_PS_MAX_WGS 2048
+int tsr_sample_scale(const float* w, int B, int mode, float* s, float* stats, void* stream);
+int tsr_pixel_loss_ps_fwd_bwd(const float* y, const float* t, int B, long long P, int kind, double param, float fg_weight,
+                              float fg_threshold, const float* s, float* pix, float* dy, float dy_scale, int accumulate,
+                              float* dt, void* stream);
+int tsr_pixel_loss_ps_fwd_bwd_wgs(const float* y, const float* t, int B, long long P, int kind, double param,
+                                  float fg_weight, float fg_threshold, const float* s, float* pix, float* dy,
+                                  float dy_scale, int accumulate, float* dt, int max_wgs, void* stream);
+int tsr_ssim_fwd_bwd_ps(const float* y, const float* t, int B, int H, int W, int win, double sigma, double C1, double C2,
+                        const float* s, float* ssim, float* dy, float dy_scale, int accumulate, void* stream);
+int tsr_weighted_mean(const float* v, const float* s, int B, float* out, void* stream);
+
 /* Rot90 / flip augmentation on the device (csrc/dihedral.hip; the reference's augmentData, utility/raw_data_process.py:57-95,
  * without storing four copies, plus the mirrored half of the dihedral group): gather sample idx[b] of src and write it
  * transformed, in one pass and one launch.

@@ -103,6 +103,11 @@ SIGNATURES = {
     "tsr_pixel_loss_fwd_bwd": [_P, _P, _L, _I, c_double, _F, _F, _P, _P, _F, _I, _P, _P, _P],
     "tsr_degrade_fwd_bwd": [_P, _I, _I, _I, _P, _L, _P, c_double, c_double, _P, _P, _P, _F, _I, _P, _P],
     "tsr_degrade_fwd_bwd_wgs": [_P, _I, _I, _I, _P, _L, _P, c_double, c_double, _P, _P, _P, _F, _I, _P, _I, _P],
+    "tsr_sample_scale": [_P, _I, _I, _P, _P, _P],
+    "tsr_pixel_loss_ps_fwd_bwd": [_P, _P, _I, _L, _I, c_double, _F, _F, _P, _P, _P, _F, _I, _P, _P],
+    "tsr_pixel_loss_ps_fwd_bwd_wgs": [_P, _P, _I, _L, _I, c_double, _F, _F, _P, _P, _P, _F, _I, _P, _I, _P],
+    "tsr_ssim_fwd_bwd_ps": [_P, _P, _I, _I, _I, _I, c_double, c_double, c_double, _P, _P, _P, _F, _I, _P],
+    "tsr_weighted_mean": [_P, _P, _I, _P, _P],
     "tsr_gather_dihedral": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
     "tsr_gather_dihedral_wgs": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
     "tsr_taxel_noise": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _I, _F, _P, _L, ctypes.c_ulonglong, ctypes.c_uint, _P],

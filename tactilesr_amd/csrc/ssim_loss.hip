@@ -33,17 +33,37 @@ __device__ __forceinline__ double ssim_block_sum(double v, double* sh) {
   return sh[0];
 }
 
+// A skipped image (s_b == 0): value 0, its dy rows 0 on overwrite and untouched on accumulate.
+template <bool HAS_DY>
+__device__ __forceinline__ void ssim_skip(float* __restrict__ ssim, float* __restrict__ dy, int n, int accumulate) {
+  if (threadIdx.x == 0) ssim[blockIdx.x] = 0.f;
+  if constexpr (HAS_DY) {
+    if (!accumulate) {
+      float* pd = dy + (size_t)blockIdx.x * n;
+      for (int i = threadIdx.x; i < n; i += SSIM_THREADS) pd[i] = 0.f;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Global form (win = 0): one window per image, g = 1/n.  The five sums and the formula are psnr_ssim_kernel's
 // (train_ops.hip), so the value is what tsr_psnr_ssim reports.
 // ------------------------------------------------------------------------------------------
-template <bool HAS_DY>
+template <bool HAS_DY, bool HAS_S>
 __global__ __launch_bounds__(SSIM_THREADS) void ssim_global_kernel(const float* __restrict__ y,
                                                                    const float* __restrict__ t, int n, double C1,
                                                                    double C2, float* __restrict__ ssim,
                                                                    float* __restrict__ dy, double dy_scale,
-                                                                   int accumulate) {
+                                                                   int accumulate, const float* __restrict__ scale) {
   __shared__ double sh[SSIM_THREADS * 5];
+  if constexpr (HAS_S) {                                     // the per-sample scale of tsr_ssim_fwd_bwd_ps
+    const float sb = scale[blockIdx.x];
+    if (sb == 0.f) {                                         // skipped: no window work, nothing of the image is read
+      ssim_skip<HAS_DY>(ssim, dy, n, accumulate);
+      return;
+    }
+    dy_scale *= (double)sb;
+  }
   const float* py = y + (size_t)blockIdx.x * n;
   const float* pt = t + (size_t)blockIdx.x * n;
   double s[5] = {0, 0, 0, 0, 0};
@@ -87,14 +107,23 @@ __global__ __launch_bounds__(SSIM_THREADS) void ssim_global_kernel(const float* 
 // The ring is what spares a 2 (WIN - 1) row halo: no map row is computed twice.  HAS_DY = false stops after step 3 and
 // keeps no ring.
 // ------------------------------------------------------------------------------------------
-template <int WIN, bool HAS_DY>
+template <int WIN, bool HAS_DY, bool HAS_S>
 __global__ __launch_bounds__(SSIM_THREADS) void ssim_win_kernel(const float* __restrict__ y,
                                                                 const float* __restrict__ t, int H, int W, int rows,
                                                                 ssim_gauss gw, double C1, double C2,
                                                                 float* __restrict__ ssim, float* __restrict__ dy,
-                                                                double dy_scale, int accumulate) {
+                                                                double dy_scale, int accumulate,
+                                                                const float* __restrict__ s) {
   extern __shared__ double ssim_smem[];
   __shared__ double sred[SSIM_THREADS];
+  if constexpr (HAS_S) {
+    const float sb = s[blockIdx.x];
+    if (sb == 0.f) {
+      ssim_skip<HAS_DY>(ssim, dy, H * W, accumulate);
+      return;
+    }
+    dy_scale *= (double)sb;
+  }
   constexpr int PAD = WIN - 1;
   const int Ho = H - PAD, Wo = W - PAD, ring = rows + PAD;
   double* sV = ssim_smem;                                              // [5][rows][W]; sD [3][rows][Wo] aliases it
@@ -222,36 +251,38 @@ int ssim_win_rows(int H, int W, int win, bool has_dy, size_t* smem) {
   return rows;
 }
 
-template <int WIN, bool HAS_DY>
+template <int WIN, bool HAS_DY, bool HAS_S>
 int ssim_win_launch(const float* y, const float* t, int B, int H, int W, const ssim_gauss& gw, double C1, double C2,
-                    float* ssim, float* dy, double dy_scale, int accumulate, hipStream_t st) {
+                    float* ssim, float* dy, double dy_scale, int accumulate, const float* s, hipStream_t st) {
   size_t smem = 0;
   const int rows = ssim_win_rows(H, W, WIN, HAS_DY, &smem);
   if (smem > SSIM_SMEM_LARGE) return TSR_ERR_ARG;
   if (smem > 64 * 1024) {
     static bool attr_set = false;
     if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)ssim_win_kernel<WIN, HAS_DY>, hipFuncAttributeMaxDynamicSharedMemorySize,
+      (void)hipFuncSetAttribute((const void*)ssim_win_kernel<WIN, HAS_DY, HAS_S>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)SSIM_SMEM_LARGE);
       attr_set = true;
     }
   }
-  hipLaunchKernelGGL((ssim_win_kernel<WIN, HAS_DY>), dim3(B), dim3(SSIM_THREADS), smem, st, y, t, H, W, rows, gw, C1, C2,
-                     ssim, dy, dy_scale, accumulate);
+  hipLaunchKernelGGL((ssim_win_kernel<WIN, HAS_DY, HAS_S>), dim3(B), dim3(SSIM_THREADS), smem, st, y, t, H, W, rows, gw, C1, C2,
+                     ssim, dy, dy_scale, accumulate, s);
   return tsr_check_launch();
 }
 
 template <int WIN>
 int ssim_win_dispatch(const float* y, const float* t, int B, int H, int W, const ssim_gauss& gw, double C1, double C2,
-                      float* ssim, float* dy, double dy_scale, int accumulate, hipStream_t st) {
-  return dy ? ssim_win_launch<WIN, true>(y, t, B, H, W, gw, C1, C2, ssim, dy, dy_scale, accumulate, st)
-            : ssim_win_launch<WIN, false>(y, t, B, H, W, gw, C1, C2, ssim, dy, dy_scale, accumulate, st);
+                      float* ssim, float* dy, double dy_scale, int accumulate, const float* s, hipStream_t st) {
+  if (s)      // the unscaled instantiations are the kernels as they were before the scale existed
+    return dy ? ssim_win_launch<WIN, true, true>(y, t, B, H, W, gw, C1, C2, ssim, dy, dy_scale, accumulate, s, st)
+              : ssim_win_launch<WIN, false, true>(y, t, B, H, W, gw, C1, C2, ssim, dy, dy_scale, accumulate, s, st);
+  return dy ? ssim_win_launch<WIN, true, false>(y, t, B, H, W, gw, C1, C2, ssim, dy, dy_scale, accumulate, s, st)
+            : ssim_win_launch<WIN, false, false>(y, t, B, H, W, gw, C1, C2, ssim, dy, dy_scale, accumulate, s, st);
 }
 
-}  // namespace
-
-extern "C" int tsr_ssim_fwd_bwd(const float* y, const float* t, int B, int H, int W, int win, double sigma, double C1,
-                                double C2, float* ssim, float* dy, float dy_scale, int accumulate, void* stream) {
+// tsr_ssim_fwd_bwd (s NULL) and tsr_ssim_fwd_bwd_ps: one argument check, one launch.
+int ssim_entry(const float* y, const float* t, int B, int H, int W, int win, double sigma, double C1, double C2,
+               float* ssim, float* dy, float dy_scale, int accumulate, const float* s, void* stream) {
   if (!y || !t || !ssim || B <= 0 || H <= 0 || W <= 0) return TSR_ERR_ARG;
   if (!(C1 > 0) || !(C2 > 0) || dy_scale != dy_scale) return TSR_ERR_ARG;          // !(c > 0) catches NaN
   if (accumulate != 0 && accumulate != 1) return TSR_ERR_ARG;
@@ -259,12 +290,16 @@ extern "C" int tsr_ssim_fwd_bwd(const float* y, const float* t, int B, int H, in
   if (win == 0) {
     if ((long long)H * W > (1LL << 28)) return TSR_ERR_ARG;
     const int n = H * W;
-    if (dy)
-      hipLaunchKernelGGL(ssim_global_kernel<true>, dim3(B), dim3(SSIM_THREADS), 0, st, y, t, n, C1, C2, ssim, dy,
-                         (double)dy_scale, accumulate);
+    const dim3 grid(B), block(SSIM_THREADS);
+    const double sc = (double)dy_scale;
+    if (dy && s)
+      hipLaunchKernelGGL((ssim_global_kernel<true, true>), grid, block, 0, st, y, t, n, C1, C2, ssim, dy, sc, accumulate, s);
+    else if (dy)
+      hipLaunchKernelGGL((ssim_global_kernel<true, false>), grid, block, 0, st, y, t, n, C1, C2, ssim, dy, sc, accumulate, s);
+    else if (s)
+      hipLaunchKernelGGL((ssim_global_kernel<false, true>), grid, block, 0, st, y, t, n, C1, C2, ssim, dy, sc, accumulate, s);
     else
-      hipLaunchKernelGGL(ssim_global_kernel<false>, dim3(B), dim3(SSIM_THREADS), 0, st, y, t, n, C1, C2, ssim, dy,
-                         (double)dy_scale, accumulate);
+      hipLaunchKernelGGL((ssim_global_kernel<false, false>), grid, block, 0, st, y, t, n, C1, C2, ssim, dy, sc, accumulate, s);
     return tsr_check_launch();
   }
   if (win < 3 || win > SSIM_MAX_WIN || !(win & 1)) return TSR_ERR_ARG;
@@ -279,12 +314,25 @@ extern "C" int tsr_ssim_fwd_bwd(const float* y, const float* t, int B, int H, in
   }
   if (!(sum > 0)) return TSR_ERR_ARG;                       // a sigma whose square underflows: the centre tap is 0/0
   for (int k = 0; k < win; ++k) gw.g[k] /= sum;
-  const double s = (double)dy_scale;
+  const double sc = (double)dy_scale;
   switch (win) {
-    case 3: return ssim_win_dispatch<3>(y, t, B, H, W, gw, C1, C2, ssim, dy, s, accumulate, st);
-    case 5: return ssim_win_dispatch<5>(y, t, B, H, W, gw, C1, C2, ssim, dy, s, accumulate, st);
-    case 7: return ssim_win_dispatch<7>(y, t, B, H, W, gw, C1, C2, ssim, dy, s, accumulate, st);
-    case 9: return ssim_win_dispatch<9>(y, t, B, H, W, gw, C1, C2, ssim, dy, s, accumulate, st);
-    default: return ssim_win_dispatch<11>(y, t, B, H, W, gw, C1, C2, ssim, dy, s, accumulate, st);
+    case 3: return ssim_win_dispatch<3>(y, t, B, H, W, gw, C1, C2, ssim, dy, sc, accumulate, s, st);
+    case 5: return ssim_win_dispatch<5>(y, t, B, H, W, gw, C1, C2, ssim, dy, sc, accumulate, s, st);
+    case 7: return ssim_win_dispatch<7>(y, t, B, H, W, gw, C1, C2, ssim, dy, sc, accumulate, s, st);
+    case 9: return ssim_win_dispatch<9>(y, t, B, H, W, gw, C1, C2, ssim, dy, sc, accumulate, s, st);
+    default: return ssim_win_dispatch<11>(y, t, B, H, W, gw, C1, C2, ssim, dy, sc, accumulate, s, st);
   }
+}
+
+}  // namespace
+
+extern "C" int tsr_ssim_fwd_bwd(const float* y, const float* t, int B, int H, int W, int win, double sigma, double C1,
+                                double C2, float* ssim, float* dy, float dy_scale, int accumulate, void* stream) {
+  return ssim_entry(y, t, B, H, W, win, sigma, C1, C2, ssim, dy, dy_scale, accumulate, nullptr, stream);
+}
+
+extern "C" int tsr_ssim_fwd_bwd_ps(const float* y, const float* t, int B, int H, int W, int win, double sigma, double C1,
+                                   double C2, const float* s, float* ssim, float* dy, float dy_scale, int accumulate,
+                                   void* stream) {
+  return ssim_entry(y, t, B, H, W, win, sigma, C1, C2, ssim, dy, dy_scale, accumulate, s, stream);
 }

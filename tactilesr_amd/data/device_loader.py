@@ -48,14 +48,27 @@ class DeviceSRLoader:
     each batch's sample indices -- plain, shuffled, augmented and ``"expand"`` alike; the dihedral ops leave it alone,
     the taxel centres being mirror-symmetric -- and yielded as a third element, ``(LR, HR, gamma)``, which
     ``train_one_iter`` / ``eval_func`` / ``GraphedTrainStep`` accept.  With it ``last_index`` is also kept by the plain
-    loader."""
+    loader.
+
+    ``weight`` (default ``None``: the loader as it was, draw for draw) is an optional (N,) tensor of per-sample
+    supervision weights ``w >= 0`` (0 = an unlabeled sample whose ``HR`` is a placeholder).  It is gathered with each
+    batch's sample indices exactly as ``gamma`` is, and the loader then yields 4-tuples ``(LR, HR, gamma, weight)`` with
+    ``gamma`` ``None`` when the loader has none -- the form ``train_one_iter`` / ``eval_func`` / ``GraphedTrainStep``
+    accept.  ``last_index`` is kept as with ``gamma``."""
 
     def __init__(self, LR: torch.Tensor, HR: torch.Tensor, batch_size: int, shuffle: bool = False,
                  drop_last: bool = False, seed: Optional[int] = None, device="cuda",
                  rank: int = 0, world_size: int = 1, augment=None, augment_mode: str = "random",
                  axis_mode: str = "planes", axis_cnt: int = 3, taxel_noise=None, noise_seed: Optional[int] = None,
-                 gamma: Optional[torch.Tensor] = None):
+                 gamma: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None):
         assert LR.shape[0] == HR.shape[0], "LR and HR must hold the same number of samples"
+        if weight is not None:
+            from .._lib import TactileSRHipError
+            weight = torch.as_tensor(weight)
+            if weight.dim() != 1 or weight.shape[0] != LR.shape[0]:
+                raise TactileSRHipError(f"weight must hold one value per sample, ({LR.shape[0]},), got "
+                                        f"{tuple(weight.shape)}")
+            weight = weight.float()
         if gamma is not None:
             from .._lib import TactileSRHipError
             gamma = torch.as_tensor(gamma)
@@ -103,9 +116,12 @@ class DeviceSRLoader:
             LR, HR = LR.index_select(0, idx.to(LR.device)), HR.index_select(0, idx.to(HR.device))
             if gamma is not None:
                 gamma = gamma.index_select(0, idx.to(gamma.device))
+            if weight is not None:
+                weight = weight.index_select(0, idx.to(weight.device))
         self.LR = LR.to(dev).contiguous()
         self.HR = HR.to(dev).contiguous()
         self.gamma = gamma.to(dev).contiguous() if gamma is not None else None
+        self.weight = weight.to(dev).contiguous() if weight is not None else None
         self.batch_size, self.shuffle, self.drop_last = int(batch_size), bool(shuffle), bool(drop_last)
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(0 if seed is None else int(seed))
@@ -116,23 +132,38 @@ class DeviceSRLoader:
                 self._tables = tuple(t.to(dev) for t in self._tables)
 
     @classmethod
-    def from_entries(cls, entries: List[list], batch_size: int, with_gamma: bool = False, **kw) -> "DeviceSRLoader":
+    def from_entries(cls, entries: List[list], batch_size: int, with_gamma: bool = False, with_weight: bool = False,
+                     **kw) -> "DeviceSRLoader":
         """From the generator's in-memory entries (tactilesr_amd.data.depth2tactile.synthesize).  ``with_gamma=True``
-        also reads each sample's mask width ``alphaBeta[2]`` (data/SRdataset/depth2tactile.py:114-119) into ``gamma``."""
+        also reads each sample's mask width ``alphaBeta[2]`` (data/SRdataset/depth2tactile.py:114-119) into ``gamma``.
+        ``with_weight=True`` builds ``weight``: an entry's own ``"weight"`` when it has one, else 1; an entry without
+        ``"HR"`` (a recorded sensor frame) gets a zero ``HR`` of the set's shape and weight 0.  A set in which no entry
+        has an ``HR`` is refused (there is no shape to take)."""
         LR = torch.stack([torch.as_tensor(e[0]["LR"]) for e in entries])
-        HR = torch.stack([torch.as_tensor(e[0]["HR"]) for e in entries])
+        if with_weight:
+            from .._lib import TactileSRHipError
+            have = [torch.as_tensor(e[0]["HR"]) for e in entries if "HR" in e[0]]
+            if not have:
+                raise TactileSRHipError("with_weight=True: no entry of the set has an HR (nothing gives the HR shape)")
+            blank = torch.zeros_like(have[0])
+            HR = torch.stack([torch.as_tensor(e[0]["HR"]) if "HR" in e[0] else blank for e in entries])
+            kw["weight"] = torch.tensor([(float(e[0].get("weight", 1.0)) if "HR" in e[0] else 0.0) for e in entries],
+                                        dtype=torch.float32)
+        else:
+            HR = torch.stack([torch.as_tensor(e[0]["HR"]) for e in entries])
         if with_gamma:                           # the third entry of the generator's alphaBeta row is the mask width
             kw["gamma"] = torch.tensor([float(np.asarray(e[0]["alphaBeta"]).reshape(-1)[2]) for e in entries],
                                        dtype=torch.float32)
         return cls(LR, HR, batch_size, **kw)
 
     @classmethod
-    def from_file(cls, path: str, batch_size: int, with_gamma: bool = False, **kw) -> "DeviceSRLoader":
+    def from_file(cls, path: str, batch_size: int, with_gamma: bool = False, with_weight: bool = False,
+                  **kw) -> "DeviceSRLoader":
         """From a dataset file in the reference's on-disk format (an object ``.npy`` of ``{'LR','HR',...}`` dicts)
         written by ``save_dataset``.  Object arrays are pickles: only load files you wrote."""
         arr = np.load(path, allow_pickle=True)
         entries = [[arr[i].item() if arr[i].shape == () else arr[i, 0]] for i in range(len(arr))]
-        return cls.from_entries(entries, batch_size, with_gamma=with_gamma, **kw)
+        return cls.from_entries(entries, batch_size, with_gamma=with_gamma, with_weight=with_weight, **kw)
 
     def __len__(self) -> int:
         n = self._virtual_len()
@@ -167,7 +198,10 @@ class DeviceSRLoader:
             if self._noise is not None:                                 # the virtual index: (sample, op) pairs differ under "expand"
                 Fh.taxel_noise(lr, self._noise, self.noise_seed, epoch, ids=order[lo:hi], out=lr)
             hr = Fh.dihedral(self.HR, op, idx, op_mask=self._op_mask)
-            if self.gamma is not None:
+            if self.weight is not None:
+                yield (lr, hr, self.gamma.index_select(0, idx) if self.gamma is not None else None,
+                       self.weight.index_select(0, idx))
+            elif self.gamma is not None:
                 yield lr, hr, self.gamma.index_select(0, idx)
             else:
                 yield lr, hr
@@ -193,7 +227,11 @@ class DeviceSRLoader:
                 lr, hr = self.LR.index_select(0, idx), self.HR.index_select(0, idx)
                 if self._noise is not None:
                     Fh.taxel_noise(lr, self._noise, self.noise_seed, epoch, ids=idx, out=lr)
-            if self.gamma is not None:
+            if self.weight is not None:
+                self.last_index = idx if order is not None else self._identity()[lo:hi]
+                pick = (lambda v: v.index_select(0, idx)) if order is not None else (lambda v: v[lo:hi])
+                yield lr, hr, (pick(self.gamma) if self.gamma is not None else None), pick(self.weight)
+            elif self.gamma is not None:
                 self.last_index = idx if order is not None else self._identity()[lo:hi]
                 yield lr, hr, (self.gamma.index_select(0, idx) if order is not None else self.gamma[lo:hi])
             else:

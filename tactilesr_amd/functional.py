@@ -60,13 +60,21 @@ def mse_loss(y: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return _MSE.apply(y.float(), target)
 
 
-def _ssim_launch(y: torch.Tensor, t: torch.Tensor, data_range, window, sigma, K1, K2, dy, dy_scale, accumulate):
+def _ssim_launch(y: torch.Tensor, t: torch.Tensor, data_range, window, sigma, K1, K2, dy, dy_scale, accumulate,
+                 scale=None):
     """One ``tsr_ssim_fwd_bwd`` launch on contiguous fp32 (B,1,H,W) tensors: the per-sample values; ``dy`` (or None)
-    is written / accumulated in place."""
+    is written / accumulated in place.  With ``scale`` (the (B,) fp32 device vector of ``sample_scale``) the launch is
+    ``tsr_ssim_fwd_bwd_ps``: sample ``b``'s gradient is multiplied by ``scale[b]`` and a sample whose scale is 0 is
+    skipped."""
     if y.dim() != 4 or y.shape[1] != 1 or t.shape != y.shape:
         raise TactileSRHipError(f"ssim needs two (B,1,H,W) tensors of one shape, got {tuple(y.shape)} and {tuple(t.shape)}")
     B, _, H, W = y.shape
     vals = torch.empty(B, dtype=torch.float32, device=y.device)
+    if scale is not None:
+        call("tsr_ssim_fwd_bwd_ps", ptr(y), ptr(t), _I(B), _I(H), _I(W), _I(int(window)), _D(float(sigma)),
+             _D((K1 * data_range) ** 2), _D((K2 * data_range) ** 2), ptr(scale), ptr(vals), ptr(dy), _F(dy_scale),
+             _I(accumulate), stream())
+        return vals
     call("tsr_ssim_fwd_bwd", ptr(y), ptr(t), _I(B), _I(H), _I(W), _I(int(window)), _D(float(sigma)),
          _D((K1 * data_range) ** 2), _D((K2 * data_range) ** 2), ptr(vals), ptr(dy), _F(dy_scale), _I(accumulate),
          stream())
@@ -186,6 +194,102 @@ def pixel_loss(y: torch.Tensor, target: torch.Tensor, kind: str = "mse", param=N
     if target.requires_grad and target.dtype != torch.float32:
         raise TactileSRHipError("pixel_loss: a target that requires grad must be fp32")
     return _PixelLoss.apply(y.float(), target, kind, param, fg_weight, fg_threshold)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Per-sample supervision weights (tsr_sample_scale, tsr_pixel_loss_ps_fwd_bwd, tsr_ssim_fwd_bwd_ps, tsr_weighted_mean):
+# sample b of a batch counts in the pixel and SSIM terms with a weight w_b >= 0; w_b = 0 is an unlabeled sample whose
+# target is never read.
+# ----------------------------------------------------------------------------------------------------------------------
+SAMPLE_WEIGHT_NORMS = {"sum": 0, "batch": 1}
+PIXEL_LOSS_PS_MAX_WGS = 2048                                    # TSR_PIXEL_LOSS_PS_MAX_WGS of include/tactilesr_hip.h
+
+
+def sample_weight_norm_arg(norm="sum") -> str:
+    """The normalisation mode as a key of ``SAMPLE_WEIGHT_NORMS``, or ``TactileSRHipError``.  Host-only."""
+    name = str(norm).lower()
+    if name not in SAMPLE_WEIGHT_NORMS:
+        raise TactileSRHipError(f"sample_weight_norm {norm!r} is not one of {sorted(SAMPLE_WEIGHT_NORMS)}")
+    return name
+
+
+def _sample_vector(w, B: int, device, who: str, what: str = "sample weight") -> torch.Tensor:
+    if not isinstance(w, torch.Tensor) or w.dim() != 1 or w.shape[0] != B:
+        raise TactileSRHipError(f"{who}: the {what} is a ({B},) tensor, got "
+                                f"{tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__}")
+    if not w.is_cuda or w.device != device:
+        raise TactileSRHipError(f"{who}: the {what} must be on the ROCm device of the images (no CPU fallback)")
+    return w.detach().float().contiguous()
+
+
+def sample_scale(w: torch.Tensor, norm: str = "sum"):
+    """``(s (B,), stats (2,))`` of a (B,) device weight vector from one ``tsr_sample_scale`` launch.  A weight is valid
+    when it is finite and >= 0.  ``norm="sum"``: ``s_b = w_b * B / D`` with ``D`` the fp64 sum of the valid weights (0
+    when ``D == 0``), so a term ``(1/B) sum_b s_b x_b`` is the mean of ``x`` over the labeled weight; ``norm="batch"``:
+    ``s_b = w_b``, the divisor stays ``B`` (the mode whose average over data-parallel ranks is exact).  An invalid
+    weight gives ``s_b = NaN`` and is left out of ``D``.  ``stats = (D, number of valid weights > 0)``."""
+    mode = SAMPLE_WEIGHT_NORMS[sample_weight_norm_arg(norm)]
+    if not isinstance(w, torch.Tensor) or not w.is_cuda:
+        raise TactileSRHipError("sample_scale needs a ROCm tensor (no CPU fallback)")
+    w = _sample_vector(w, w.shape[0] if w.dim() == 1 else -1, w.device, "sample_scale")
+    B = w.shape[0]
+    if B == 0:
+        raise TactileSRHipError("sample_scale: an empty weight vector")
+    s = torch.empty(B, dtype=torch.float32, device=w.device)
+    stats = torch.empty(2, dtype=torch.float32, device=w.device)
+    call("tsr_sample_scale", ptr(w), _I(B), _I(mode), ptr(s), ptr(stats), stream())
+    return s, stats
+
+
+def weighted_mean(v: torch.Tensor, scale=None) -> torch.Tensor:
+    """``(1/B) sum_{scale_b != 0} scale_b v_b`` as a (1,) tensor from one ``tsr_weighted_mean`` launch (fp64, index
+    order, one rounding); ``scale=None``: the plain mean.  An entry whose scale is 0 is not read: a NaN there stays out."""
+    if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dim() != 1 or v.shape[0] == 0:
+        raise TactileSRHipError("weighted_mean needs a non-empty (B,) ROCm tensor (no CPU fallback)")
+    v = v.detach().float().contiguous()
+    if scale is not None:
+        scale = _sample_vector(scale, v.shape[0], v.device, "weighted_mean", "scale")
+    out = torch.empty(1, dtype=torch.float32, device=v.device)
+    call("tsr_weighted_mean", ptr(v), ptr(scale), _I(v.shape[0]), ptr(out), stream())
+    return out
+
+
+def pixel_loss_per_sample(y: torch.Tensor, target: torch.Tensor, kind: str = "mse", param=None, fg_weight: float = 0.0,
+                          fg_threshold: float = 0.0, scale=None, dy=None, dy_scale: float = 1.0, accumulate: bool = False,
+                          want_dt: bool = False, max_wgs=None):
+    """The per-sample form of ``pixel_loss_fwd_bwd`` from one ``tsr_pixel_loss_ps_fwd_bwd`` launch, outside autograd:
+    ``(pix (B,), dy)`` or, with ``want_dt``, ``(pix, dy, dt)``.  ``pix_b`` is sample ``b``'s own mean over its
+    ``P = numel / B`` elements (not multiplied by its scale).  ``dy = dy_scale * scale_b * d pix_b / d y / B``: with
+    ``scale=None`` (all ones) the gradient of ``mean_b pix_b``, bit for bit ``pixel_loss_fwd_bwd``'s.  ``scale`` is the
+    (B,) device vector of ``sample_scale``; a sample whose scale is 0 is skipped -- its ``y`` and ``target`` are not
+    read, its ``pix`` is 0, its ``dy`` rows are 0 (untouched with ``accumulate=True``) and its ``dt`` rows 0.
+    ``max_wgs`` caps the grid (the result does not depend on it)."""
+    if not y.is_cuda or not target.is_cuda:
+        raise TactileSRHipError("pixel_loss_per_sample needs ROCm tensors (no CPU fallback)")
+    name, p, w, thr = pixel_loss_args(kind, param, fg_weight, fg_threshold)
+    y = y.detach().float().contiguous()
+    t = target.detach().float().contiguous()
+    if t.shape != y.shape or y.dim() < 1 or y.numel() == 0:
+        raise TactileSRHipError(f"pixel loss needs two non-empty tensors of one shape, got {tuple(y.shape)} and "
+                                f"{tuple(t.shape)}")
+    B = y.shape[0]
+    if scale is not None:
+        scale = _sample_vector(scale, B, y.device, "pixel_loss_per_sample", "scale")
+    if dy is None:
+        if accumulate:
+            raise TactileSRHipError("pixel_loss_per_sample: accumulate=True needs the dy to add to")
+        dy = torch.empty_like(y)
+    elif dy.dtype != torch.float32 or dy.shape != y.shape:
+        raise TactileSRHipError("pixel_loss_per_sample: dy must be an fp32 tensor of y's shape")
+    dt = torch.empty_like(y) if want_dt else None
+    pix = torch.empty(B, dtype=torch.float32, device=y.device)
+    args = [ptr(y), ptr(t), _I(B), _L(y.numel() // B), _I(PIXEL_KINDS[name]), _D(0.0 if p is None else p), _F(w), _F(thr),
+            ptr(scale), ptr(pix), ptr(dy), _F(dy_scale), _I(1 if accumulate else 0), ptr(dt)]
+    if max_wgs is None:
+        call("tsr_pixel_loss_ps_fwd_bwd", *args, stream())
+    else:
+        call("tsr_pixel_loss_ps_fwd_bwd_wgs", *args, _I(int(max_wgs)), stream())
+    return (pix, dy, dt) if want_dt else (pix, dy)
 
 
 def _plain_mse(pixel_kind, fg_weight) -> bool:
@@ -338,6 +442,7 @@ def degradation_loss(y: torch.Tensor, z: torch.Tensor, gamma, gain: float = 1.0)
 def sr_loss_fwd_bwd(y: torch.Tensor, target: torch.Tensor, ssim_weight: float = 0.0, data_range: float = 1.0,
                     window: int = 11, sigma: float = 1.5, K1: float = 0.01, K2: float = 0.03, return_parts: bool = False,
                     pixel_kind: str = "mse", pixel_param=None, fg_weight: float = 0.0, fg_threshold: float = 0.0,
+                    sample_weight=None, sample_weight_norm: str = "sum",
                     deg_weight: float = 0.0, deg_z=None, deg_gamma=None, deg_gain: float = 1.0):
     """``pixel(y, target) + ssim_weight * (1 - mean_b ssim_b) + deg_weight * mean_b q_b`` and its gradient w.r.t. ``y``,
     outside autograd: ``(loss (1,), dy)``.  The pixel launch, then the SSIM launch accumulating
@@ -347,12 +452,43 @@ def sr_loss_fwd_bwd(y: torch.Tensor, target: torch.Tensor, ssim_weight: float = 
     ``pixel_loss_fwd_bwd`` with the four pixel arguments; ``ssim_weight == 0`` and ``deg_weight == 0`` is that launch
     alone, launch for launch, and ``deg_weight == 0`` issues exactly the launches it issued before the term existed.
     ``return_parts=True`` appends the terms: ``(loss, dy, pixel (1,), ssim (B,) or None)`` and, with a non-zero
-    ``deg_weight``, ``q (B,)`` as a fifth."""
+    ``deg_weight``, ``q (B,)`` as a fifth.
+
+    ``sample_weight`` (default ``None``: exactly the launches above) is a (B,) device tensor of supervision weights
+    ``w_b >= 0``.  With ``s = sample_scale(sample_weight, sample_weight_norm)`` the loss is
+    ``(1/B) sum_{s_b != 0} s_b [pix_b + ssim_weight (1 - ssim_b)] + deg_weight * mean_b q_b``: the pixel and SSIM terms
+    count sample ``b`` with ``s_b``, the degradation term keeps counting every sample, and the target of a sample with
+    ``w_b = 0`` is never read (it may hold NaN).  The launches are then: the scale launch, the per-sample pixel launch
+    (``pixel_loss_per_sample``, the plain MSE as kind ``"mse"``), the SSIM launch in its ``_ps`` form accumulating, the
+    unchanged degradation launch, and the weighted means (``weighted_mean``).  ``return_parts`` reports the weighted
+    pixel term ``(1/B) sum s_b pix_b`` as ``pixel`` and appends three more: the per-sample ``pix (B,)``, ``s (B,)`` and
+    the ``stats (2,)`` of ``sample_scale``."""
     if not y.is_cuda or not target.is_cuda:
         raise TactileSRHipError("sr_loss_fwd_bwd needs ROCm tensors (no CPU fallback)")
     deg = float(deg_weight) != 0
     if deg and (deg_z is None or deg_gamma is None):
         raise TactileSRHipError("sr_loss_fwd_bwd: a non-zero deg_weight needs deg_z and deg_gamma")
+    if sample_weight is not None:
+        norm = sample_weight_norm_arg(sample_weight_norm)
+        B = y.shape[0]
+        s, stats = sample_scale(_sample_vector(sample_weight, B, y.device, "sr_loss_fwd_bwd"), norm)
+        pix_b, dy = pixel_loss_per_sample(y, target, pixel_kind, pixel_param, fg_weight, fg_threshold, scale=s)
+        per_sample, vals, q = pix_b, None, None
+        if ssim_weight != 0:
+            t = target.detach().float().contiguous()
+            vals = _ssim_launch(y.contiguous(), t, data_range, window, sigma, K1, K2, dy, -float(ssim_weight) / B, 1,
+                                scale=s)
+            per_sample = pix_b + float(ssim_weight) * (1.0 - vals)
+        if deg:
+            q = degradation_fwd_bwd(y, deg_z, deg_gamma, deg_gain, dy=dy, dy_scale=float(deg_weight) / B,
+                                    accumulate=True)[0]
+        loss = weighted_mean(per_sample, s)
+        pix = weighted_mean(pix_b, s) if (return_parts and per_sample is not pix_b) else loss
+        if deg:
+            loss = loss + float(deg_weight) * q.mean()
+        if not return_parts:
+            return loss, dy
+        return (loss, dy, pix, vals) + ((q,) if deg else ()) + (pix_b, s, stats)
     if _plain_mse(pixel_kind, fg_weight):
         mse, dy = mse_fwd_bwd(y, target)
     else:
@@ -373,14 +509,18 @@ def sr_loss_fwd_bwd(y: torch.Tensor, target: torch.Tensor, ssim_weight: float = 
 class _SRLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, target, ssim_weight, data_range, window, sigma, pixel_kind, pixel_param, fg_weight, fg_threshold,
-                deg_weight, deg_z, deg_gamma, deg_gain):
+                deg_weight, deg_z, deg_gamma, deg_gain, sample_weight=None, sample_weight_norm="sum"):
         parts = sr_loss_fwd_bwd(y, target, ssim_weight, data_range, window, sigma, return_parts=True,
                                 pixel_kind=pixel_kind, pixel_param=pixel_param, fg_weight=fg_weight,
                                 fg_threshold=fg_threshold, deg_weight=deg_weight, deg_z=deg_z, deg_gamma=deg_gamma,
-                                deg_gain=deg_gain)
+                                deg_gain=deg_gain, sample_weight=sample_weight, sample_weight_norm=sample_weight_norm)
         loss, dy, mse, vals = parts[:4]
         ctx.save_for_backward(dy)
         mse0 = mse[0]
+        if sample_weight is not None:            # (..., [q,] pix_b, s, stats): everything but the loss is a report
+            rest = parts[4:]
+            ctx.mark_non_differentiable(mse0, *([vals] if vals is not None else []), *rest)
+            return (loss[0], mse0, vals) + tuple(rest)
         if len(parts) == 5:
             ctx.mark_non_differentiable(mse0, vals, parts[4]) if vals is not None else \
                 ctx.mark_non_differentiable(mse0, parts[4])
@@ -391,23 +531,30 @@ class _SRLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout, *_gparts):
         (dy,) = ctx.saved_tensors
-        return (dy * gout,) + (None,) * 13
+        return (dy * gout,) + (None,) * 15
 
 
 def sr_loss(y: torch.Tensor, target: torch.Tensor, ssim_weight: float, data_range: float = 1.0, window: int = 11,
             sigma: float = 1.5, pixel_kind: str = "mse", pixel_param=None, fg_weight: float = 0.0,
-            fg_threshold: float = 0.0, deg_weight: float = 0.0, deg_z=None, deg_gamma=None, deg_gain: float = 1.0):
+            fg_threshold: float = 0.0, sample_weight=None, sample_weight_norm: str = "sum", deg_weight: float = 0.0,
+            deg_z=None, deg_gamma=None, deg_gain: float = 1.0):
     """The autograd form of ``sr_loss_fwd_bwd`` for a non-zero ``ssim_weight`` or ``deg_weight``:
     ``(loss, pixel term, per-sample ssim)`` and, with a non-zero ``deg_weight``, the per-sample ``q`` as a fourth
     (``ssim`` is then ``None`` when ``ssim_weight == 0``); only ``loss`` carries a gradient (to ``y`` -- the taxels
-    ``deg_z`` get none here: ``degradation_loss`` is the form that differentiates them)."""
+    ``deg_z`` get none here: ``degradation_loss`` is the form that differentiates them).  With ``sample_weight`` (any
+    ``ssim_weight`` and ``deg_weight``, zero included) the weighted loss of ``sr_loss_fwd_bwd``; the tuple then ends
+    with the per-sample ``pix (B,)``, the scale ``s (B,)`` and ``stats (2,)``, and its pixel term is the weighted one."""
     if not y.is_cuda:
         raise TactileSRHipError("sr_loss needs ROCm tensors (no CPU fallback)")
     if float(deg_weight) != 0 and deg_z is None:
         raise TactileSRHipError("sr_loss: a non-zero deg_weight needs deg_z and deg_gamma")
+    if sample_weight is not None:
+        return _SRLoss.apply(y.float(), target, float(ssim_weight), data_range, window, sigma, pixel_kind, pixel_param,
+                             fg_weight, fg_threshold, float(deg_weight), None if deg_z is None else deg_z.detach(),
+                             deg_gamma, float(deg_gain), sample_weight.detach(), sample_weight_norm_arg(sample_weight_norm))
     return _SRLoss.apply(y.float(), target, float(ssim_weight), data_range, window, sigma, pixel_kind, pixel_param,
                          fg_weight, fg_threshold, float(deg_weight), None if deg_z is None else deg_z.detach(), deg_gamma,
-                         float(deg_gain))
+                         float(deg_gain), None, "sum")
 
 
 def psnr_ssim(a: torch.Tensor, b: torch.Tensor, maxValue: float, reference_quirk: bool = True,

@@ -52,6 +52,11 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
   (the default) captures the step as before.
 * Per-sample gamma: a batch may be ``(LR, HR_raw, gamma)`` with ``gamma`` (B,) fp32; it is copied into a third static
   buffer that the captured degradation launch reads, and its shape joins the batch signature.
+* Per-sample supervision weights: a batch may be ``(LR, HR_raw, gamma, weight)`` (``gamma`` may be ``None``) with
+  ``weight`` (B,) fp32; it is copied into a fourth static buffer that the captured scale launch
+  (``functional.sample_scale``) reads, so the weights are data: replays with different weights -- all-zero included --
+  need no recapture.  Its shape and dtype join the batch signature and ``sample_weight_norm`` the key (a changed norm
+  recaptures).  The returned dict is ``train_cal_loss``'s for such a batch (``labeled_weight`` included).
 * Refused (``TactileSRHipError``): eval mode, a batch whose shape / dtype differs from the first call's, an attached
   ``GradSync`` (no collectives inside a graph), ``engine.profile`` / ``engine.debug`` / ``engine.keep_ctx``, an
   optimizer other than ``tactilesr_amd.optim.Adam``, a model not on a ROCm device, a model without a trainable
@@ -66,8 +71,9 @@ from .. import functional as Fh
 from .. import optim as opt_mod
 from .._lib import TactileSRHipError
 from ..ddp import note_forward
-from .tactileSR_train import (_batch_gamma, _degradation_gamma, _prep, degradation_loss_config, pixel_is_plain_mse,
-                              pixel_loss_config, ssim_loss_config, train_one_iter)
+from .tactileSR_train import (_batch_gamma, _batch_weight, _degradation_gamma, _prep, degradation_loss_config,
+                              pixel_is_plain_mse, pixel_loss_config, sample_weight_config, ssim_loss_config,
+                              train_one_iter)
 
 _CONFIG_KEYS = ("HR_scale_num", "scale_factor", "seqsCnt", "axisCnt")      # what the captured train_cal_loss bakes in
 
@@ -97,7 +103,7 @@ class GraphedTrainStep:
 
     def _drop(self) -> None:
         self.graph = None
-        self._out = self._launches = self._hyper = self._LR = self._HR = self._G = None
+        self._out = self._launches = self._hyper = self._LR = self._HR = self._G = self._SW = None
         self._norm = self._norm_work = self._norm_table = None
         self._ema_omd = self._ema_table = None
         self._graph_key = None
@@ -115,12 +121,12 @@ class GraphedTrainStep:
         return (m.train_impl, id(arena), arena.flat.data_ptr() if arena is not None else 0,
                 tuple(t.data_ptr() for t in m.parameters()), tuple(b.data_ptr() for b in m.buffers()), groups,
                 tuple(self.config[k] for k in _CONFIG_KEYS), ssim_loss_config(self.config), pixel_loss_config(self.config),
-                degradation_loss_config(self.config), self.clip_grad_norm,
+                degradation_loss_config(self.config), sample_weight_config(self.config), self.clip_grad_norm,
                 (id(self.ema), self.ema._flat.data_ptr(), self.ema.buffers) if self.ema is not None else None,
                 tuple(p.requires_grad for p in m.parameters()),      # the captured backward holds the trainable set's launches
                 tuple(mod.training for mod in m.modules() if isinstance(mod, torch.nn.BatchNorm2d)))      # and each BatchNorm's mode
 
-    def _check(self, LR, HR, gamma=None) -> None:
+    def _check(self, LR, HR, gamma=None, weight=None) -> None:
         m = self.model
         if not m.training:
             raise TactileSRHipError("GraphedTrainStep replays the TRAIN step: the model is in eval mode")
@@ -129,10 +135,12 @@ class GraphedTrainStep:
         sig = (tuple(LR.shape), LR.dtype, tuple(HR.shape), HR.dtype)
         if gamma is not None:                    # a 3-tuple batch: the per-sample gamma is a third static input
             sig += (tuple(gamma.shape), gamma.dtype)
+        if weight is not None:                   # a 4-tuple batch: the supervision weights are a fourth static input
+            sig += ("weight", tuple(weight.shape), weight.dtype)
         if self._sig is None:
             self._sig = sig
         elif sig != self._sig:
-            raise TactileSRHipError(f"GraphedTrainStep was set up for batch (LR, HR_raw[, gamma]) of shape / dtype {self._sig}, "
+            raise TactileSRHipError(f"GraphedTrainStep was set up for batch (LR, HR_raw[, gamma[, weight]]) of shape / dtype {self._sig}, "
                                     f"got {sig}")
         eng = m.train_engine()
         if eng.grad_sync is not None:
@@ -149,7 +157,7 @@ class GraphedTrainStep:
                                         "optimizer (the norm is taken over model.parameters(), the fused clip over "
                                         "the optimizer's)")
 
-    def _capture(self, LR, HR, gamma=None) -> None:
+    def _capture(self, LR, HR, gamma=None, weight=None) -> None:
         m, opt = self.model, self.optimizer
         dev = next(m.parameters()).device
         pixel = pixel_loss_config(self.config)     # refuses a bad key before anything is captured
@@ -157,6 +165,9 @@ class GraphedTrainStep:
         if gamma is not None:
             self._G = torch.empty(gamma.shape, dtype=torch.float32, device=dev)
         deg_gamma = _degradation_gamma(deg, self._G) if deg[0] != 0 else None
+        norm = sample_weight_config(self.config)
+        if weight is not None:
+            self._SW = torch.empty(weight.shape, dtype=torch.float32, device=dev)
         self._LR = torch.empty(LR.shape, dtype=LR.dtype, device=dev)
         self._HR = torch.empty(HR.shape, dtype=HR.dtype, device=dev)
         # one row of {lr, bc1, bc2_sqrt} ({lr, bc1, bc2_sqrt, decay}: AdamW, AMSGrad) per Adam launch; at most one
@@ -185,21 +196,32 @@ class GraphedTrainStep:
             named = [(n, p) for n, p in m.named_parameters() if p.requires_grad]
             if named:
                 note_forward(eng, ctx)
-            weight, window, sigma, data_range = ssim_loss_config(self.config)
+            ssim_w, window, sigma, data_range = ssim_loss_config(self.config)
             kind, param, fg_weight, fg_threshold = pixel
-            if deg[0] == 0:
-                loss, dy, pix, vals = Fh.sr_loss_fwd_bwd(out.float(), HR, weight, data_range, window, sigma,
+            if weight is not None:               # train_cal_loss's weighted branch, on the static weight buffer
+                res = Fh.sr_loss_fwd_bwd(out.float(), HR, ssim_w, data_range, window, sigma, return_parts=True,
+                                         pixel_kind=kind, pixel_param=param, fg_weight=fg_weight,
+                                         fg_threshold=fg_threshold, deg_weight=deg[0],
+                                         deg_z=LR[:, deg[2]] if deg[0] != 0 else None, deg_gamma=deg_gamma,
+                                         deg_gain=deg[3] or 1.0, sample_weight=self._SW, sample_weight_norm=norm)
+                loss, dy, pix, vals = res[:4]
+                labeled = res[-1][0] / LR.shape[0]
+                w_ssim = Fh.weighted_mean(vals, res[-2])[0] if vals is not None else None
+                if deg[0] != 0:
+                    deg_mean = res[4].mean()
+            elif deg[0] == 0:
+                loss, dy, pix, vals = Fh.sr_loss_fwd_bwd(out.float(), HR, ssim_w, data_range, window, sigma,
                                                          return_parts=True, pixel_kind=kind, pixel_param=param,
                                                          fg_weight=fg_weight, fg_threshold=fg_threshold)
             else:                                # the z-taxels are a slice of the static LR, read in place
-                loss, dy, pix, vals, q = Fh.sr_loss_fwd_bwd(out.float(), HR, weight, data_range, window, sigma,
+                loss, dy, pix, vals, q = Fh.sr_loss_fwd_bwd(out.float(), HR, ssim_w, data_range, window, sigma,
                                                             return_parts=True, pixel_kind=kind, pixel_param=param,
                                                             fg_weight=fg_weight, fg_threshold=fg_threshold,
                                                             deg_weight=deg[0], deg_z=LR[:, deg[2]], deg_gamma=deg_gamma,
                                                             deg_gain=deg[3])
                 deg_mean = q.mean()
             # weight 0: the pixel launch alone; the plain MSE: mse_fwd_bwd
-            ssim_mean = vals.mean() if vals is not None else None
+            ssim_mean = vals.mean() if vals is not None and weight is None else None
             opt.zero_grad()
             grads = eng.backward(ctx, dy)
             del ctx
@@ -216,7 +238,13 @@ class GraphedTrainStep:
         # the launches (and the norm launch) hold the Adam chunk tables the graph reads: keep them alive with it
         out_dict = {"total_loss": loss[0]}
         pix_key = "mse_loss" if pixel_is_plain_mse(pixel) else "pixel_loss"
-        if deg[0] != 0:                          # train_cal_loss's loss_dict with a degradation term
+        if weight is not None:                   # train_cal_loss's loss_dict of a weighted batch
+            out_dict.update({pix_key: pix[0], "labeled_weight": labeled})
+            if vals is not None:
+                out_dict["ssim"] = w_ssim
+            if deg[0] != 0:
+                out_dict["degradation_loss"] = deg_mean
+        elif deg[0] != 0:                        # train_cal_loss's loss_dict with a degradation term
             out_dict.update({pix_key: pix[0], "degradation_loss": deg_mean})
             if vals is not None:
                 out_dict["ssim"] = ssim_mean
@@ -233,7 +261,8 @@ class GraphedTrainStep:
     def __call__(self, batch):
         LR, HR = batch[0], batch[1]
         gamma = _batch_gamma(batch, LR.device)
-        self._check(LR, HR, gamma)
+        weight = _batch_weight(batch, LR.device)
+        self._check(LR, HR, gamma, weight)
         if self.graph is not None and self._key() != self._graph_key:
             self._drop()
         if self.graph is None and self._eager_left > 0:
@@ -241,11 +270,13 @@ class GraphedTrainStep:
             return train_one_iter(self.model, self.optimizer, batch, self.config, clip_grad_norm=self.clip_grad_norm,
                                   ema=self.ema)
         if self.graph is None:
-            self._capture(LR, HR, gamma)
+            self._capture(LR, HR, gamma, weight)
         self._LR.copy_(LR)
         self._HR.copy_(HR)
         if gamma is not None:
             self._G.copy_(gamma)
+        if weight is not None:
+            self._SW.copy_(weight)
         rows = self.optimizer._replay_rows(self._launches)       # advances state["step"]; a fresh pinned tensor
         if self._norm_table is not None:
             self.optimizer.launches += opt_mod.GN_LAUNCHES

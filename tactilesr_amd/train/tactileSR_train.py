@@ -33,15 +33,36 @@ def _prep(batch, config, device):
 
 
 def _batch_gamma(batch, device):
-    """The (B,) fp32 per-sample gamma of a 3-tuple batch ``(LR, HR, gamma)`` on ``device``, ``None`` for a 2-tuple."""
+    """The (B,) fp32 per-sample gamma of a batch ``(LR, HR, gamma)`` or ``(LR, HR, gamma, weight)`` on ``device``;
+    ``None`` for a 2-tuple and for a 4-tuple whose ``gamma`` is ``None``."""
     if len(batch) == 2:
         return None
-    if len(batch) != 3:
-        raise TactileSRHipError(f"a batch is (LR, HR) or (LR, HR, gamma), got {len(batch)} elements")
+    if len(batch) not in (3, 4):
+        raise TactileSRHipError("a batch is (LR, HR), (LR, HR, gamma) or (LR, HR, gamma, weight) with gamma a (B,) "
+                                f"tensor or None, got {len(batch)} elements")
     g = batch[2]
+    if g is None and len(batch) == 4:
+        return None
     if not isinstance(g, torch.Tensor) or g.dim() != 1 or g.shape[0] != batch[0].shape[0]:
         raise TactileSRHipError("the third element of a batch is the per-sample gamma, a (B,) tensor")
     return g.to(device).float()
+
+
+def _batch_weight(batch, device):
+    """The (B,) fp32 supervision weights of a 4-tuple batch ``(LR, HR, gamma, weight)`` on ``device``, else ``None``."""
+    if len(batch) != 4:
+        return None
+    w = batch[3]
+    if not isinstance(w, torch.Tensor) or w.dim() != 1 or w.shape[0] != batch[0].shape[0]:
+        raise TactileSRHipError("the fourth element of a batch is the per-sample supervision weight, a (B,) tensor")
+    return w.to(device).float()
+
+
+def sample_weight_config(config):
+    """The optional key ``sample_weight_norm`` (default ``"sum"``), read when a batch carries per-sample weights:
+    ``"sum"`` makes the supervised terms means over the labeled weight, ``"batch"`` keeps the divisor ``B``
+    (``functional.sample_scale``).  An unknown value raises ``TactileSRHipError`` here, before any launch."""
+    return Fh.sample_weight_norm_arg(config.get("sample_weight_norm", "sum"))
 
 
 def ssim_loss_config(config):
@@ -128,15 +149,38 @@ def train_cal_loss(model, batch, config):
     z-taxels are the prepared ``LR[:, degradation_channel]``, detached: the term sends no gradient to ``LR``
     (``LR.grad`` holds what the pixel and SSIM terms send through the model, nothing from the residual's own
     ``d q / d z``).  A batch may be ``(LR, HR, gamma)`` with a (B,) per-sample ``gamma``, which overrides
-    ``degradation_gamma``; without the key, or with weight 0, the step is unchanged."""
+    ``degradation_gamma``; without the key, or with weight 0, the step is unchanged.
+
+    A batch may be ``(LR, HR, gamma, weight)`` (``gamma`` may be ``None``) with (B,) supervision weights ``w_b >= 0``:
+    the pixel and SSIM terms count sample ``b`` with the scale ``s_b`` of ``functional.sample_scale`` under the config's
+    ``sample_weight_norm`` (``sample_weight_config``), the degradation term keeps counting every sample, and the ``HR``
+    of a sample with ``w_b = 0`` is never read by the loss (it may hold anything).  The dict then holds the weighted
+    pixel term ``(1/B) sum_b s_b pix_b`` under its usual key, the weighted ``ssim`` ``(1/B) sum_b s_b ssim_b`` with an
+    SSIM term, ``labeled_weight`` (the sum of the valid weights / B) and ``degradation_loss`` with that term; the plain
+    MSE setting runs the per-sample launch with kind ``"mse"``."""
     device = next(model.parameters()).device
     pixel = pixel_loss_config(config)
     deg = degradation_loss_config(config)
+    sw = _batch_weight(batch, device)
+    norm = sample_weight_config(config) if sw is not None else None
     gamma = _degradation_gamma(deg, _batch_gamma(batch, device)) if deg[0] != 0 else None
     LR, HR = _prep(batch, config, device)
     out = model(LR)
     weight, window, sigma, data_range = ssim_loss_config(config)
     plain = pixel_is_plain_mse(pixel)
+    if sw is not None:
+        res = Fh.sr_loss(out, HR, weight, data_range, window, sigma, *pixel, deg_weight=deg[0],
+                         deg_z=LR.detach()[:, deg[2]] if deg[0] != 0 else None, deg_gamma=gamma, deg_gain=deg[3] or 1.0,
+                         sample_weight=sw, sample_weight_norm=norm)
+        loss, pix, vals = res[:3]
+        s, stats = res[-2], res[-1]
+        d = {"total_loss": loss, "mse_loss" if plain else "pixel_loss": pix,
+             "labeled_weight": stats[0] / LR.shape[0]}
+        if vals is not None:
+            d["ssim"] = Fh.weighted_mean(vals, s)[0]
+        if deg[0] != 0:
+            d["degradation_loss"] = res[3].mean()
+        return loss, d
     if deg[0] != 0:
         res = Fh.sr_loss(out, HR, weight, data_range, window, sigma, *pixel, deg_weight=deg[0],
                          deg_z=LR.detach()[:, deg[2]], deg_gamma=gamma, deg_gain=deg[3])
@@ -234,7 +278,13 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
     that is on: the batch-averaged ``mean_b q_b`` of ``functional.degradation_fwd_bwd`` between the output pooled onto
     the taxels and the (noisy, when ``taxel_noise`` is on) z-taxels the model saw -- a score that needs no HR.  It reads
     ``degradation_gamma`` / ``degradation_channel`` / ``degradation_gain`` of ``degradation_loss_config`` whatever the
-    weight; a 3-tuple batch's per-sample ``gamma`` overrides the key."""
+    weight; a 3-tuple batch's per-sample ``gamma`` overrides the key.
+
+    Batches that carry a weight (4-tuples) turn the loss, SSIM, PSNR and windowed SSIM into
+    ``sum_b w_b m_b / sum_b w_b`` over the whole set, from the per-sample values (``functional.pixel_loss_per_sample``,
+    ``psnr_ssim``, ``ssim``) through ``functional.weighted_mean``: a sample with ``w_b = 0`` stays out even when its
+    metric is NaN (its ``HR`` may hold anything), and a set whose weights sum to 0 returns NaN for these averages.  The
+    degradation score stays the plain mean over all samples.  Without weights the results are unchanged."""
     if ema is not None:
         with ema.applied():
             return eval_func(model, test_loader, config, windowed_ssim, self_ensemble, None, taxel_noise, noise_seed,
@@ -248,25 +298,50 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
     tot_loss = tot_ssim = tot_psnr = tot_wssim = 0.0
     n = 0
     _, window, sigma, data_range = ssim_loss_config(config)
+    weighted = None              # whether the set's batches carry weights: all of them or none
+    tot_w = 0.0
     for batch in test_loader:
         LR, HR = _prep(batch, config, device)
         if noise is not None:
             LR = Fh.taxel_noise(LR, noise, noise_seed, 0, id_base=seen)
             seen += LR.shape[0]
         out = model(LR) if self_ensemble is None else Fh.self_ensemble(model, LR.contiguous(), self_ensemble)
-        tot_loss += float(Fh.mse_loss(out, HR))
-        ps, ss = Fh.psnr_ssim(out, HR, config["sensorMaxVaule_factor"], reference_quirk=True)
-        tot_psnr += float(ps.mean())
-        tot_ssim += float(ss.mean())
-        if windowed_ssim:
-            tot_wssim += float(Fh.ssim(out, HR, data_range, window, sigma).mean())
+        sw = _batch_weight(batch, device)
+        if weighted is None:
+            weighted = sw is not None
+        elif weighted != (sw is not None):
+            raise TactileSRHipError("eval_func: some batches of the set carry a weight and some do not")
+        if sw is not None:       # sums of w_b m_b: the "batch" scale is w_b itself, and weighted_mean divides by B
+            B = LR.shape[0]
+            s, stats = Fh.sample_scale(sw, "batch")
+            mse_b = Fh.pixel_loss_per_sample(out, HR, "mse", scale=s)[0]
+            ps, ss = Fh.psnr_ssim(out, HR, config["sensorMaxVaule_factor"], reference_quirk=True)
+            tot_loss += B * float(Fh.weighted_mean(mse_b, s))
+            tot_psnr += B * float(Fh.weighted_mean(ps, s))
+            tot_ssim += B * float(Fh.weighted_mean(ss, s))
+            if windowed_ssim:
+                tot_wssim += B * float(Fh.weighted_mean(Fh.ssim(out, HR, data_range, window, sigma), s))
+            tot_w += float(stats[0])
+        else:
+            tot_loss += float(Fh.mse_loss(out, HR))
+            ps, ss = Fh.psnr_ssim(out, HR, config["sensorMaxVaule_factor"], reference_quirk=True)
+            tot_psnr += float(ps.mean())
+            tot_ssim += float(ss.mean())
+            if windowed_ssim:
+                tot_wssim += float(Fh.ssim(out, HR, data_range, window, sigma).mean())
         if degradation:
             gamma = _degradation_gamma(deg, _batch_gamma(batch, device))
             tot_deg += float(Fh.degradation_fwd_bwd(out, LR[:, deg[2]], gamma, deg[3], want_dy=False)[0].mean())
         n += 1
-    res = (tot_loss / n, tot_ssim / n, tot_psnr / n)
-    if windowed_ssim:
-        res += (tot_wssim / n,)
+    if weighted:
+        avg = (lambda v: v / tot_w) if tot_w > 0 else (lambda v: float("nan"))
+        res = (avg(tot_loss), avg(tot_ssim), avg(tot_psnr))
+        if windowed_ssim:
+            res += (avg(tot_wssim),)
+    else:
+        res = (tot_loss / n, tot_ssim / n, tot_psnr / n)
+        if windowed_ssim:
+            res += (tot_wssim / n,)
     if degradation:
         res += (tot_deg / n,)
     return res

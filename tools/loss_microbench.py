@@ -26,7 +26,18 @@ buffers at B = 32 and B = 8192 of 1x40x40 and 1x100x100 -- the forward alone, an
 train step calls it -- against the same term and its gradient composed from torch ops in fp32 through autograd (the mask
 tables prepared once outside the timing; per call two batched matmuls, the mask floor, the residual and the MSE); and
 the B = 32 train step, eager and graph-replayed, without the key (the step as it was before the term existed) and with
-``degradation_loss_weight`` 0.1."""
+``degradation_loss_weight`` 0.1.
+
+    python tools/loss_microbench.py --sample-weight [--rounds R] [--out profiles/sample_weight_cost.json]
+times the per-sample supervision weights instead, in one process, at B = 32 and B = 8192 of 1x40x40 and 1x100x100 with
+the L1 pixel term and the SSIM term (weight 0.1, window 11): the weighted launch set as ``sr_loss_fwd_bwd`` issues it
+(tsr_sample_scale, tsr_pixel_loss_ps_fwd_bwd, tsr_ssim_fwd_bwd_ps accumulating, tsr_weighted_mean) with all weights 1
+with a random half of the weights 0 and with every second weight 0 (workgroup b takes image b and the hardware deals
+workgroups to the eight XCDs in turn, so that pattern leaves four of them idle); the unweighted launch pair of the same call without a weight (tsr_pixel_loss_fwd_bwd +
+tsr_ssim_fwd_bwd: the entry points the step had before the weights -- run from this build, not from the parent
+commit's binary); the same weighted loss and its gradient composed from torch ops in fp32 through autograd; and the
+B = 32 train step, eager and graph-replayed, on a 2-tuple batch and on a 4-tuple batch with all weights 1 and with a
+random half of them 0."""
 import argparse
 import json
 import os
@@ -299,6 +310,96 @@ def degradation_step_cases(a):
     return cases
 
 
+SW_SHAPES = ((32, 40, 40), (8192, 40, 40), (32, 100, 100), (8192, 100, 100))
+SW_KIND = "l1"
+
+
+def torch_weighted(y, t, w, data_range):
+    """The weighted L1 + SSIM loss ("sum" normalisation) and its gradient from torch ops through autograd.  The
+    composition has no way to skip a sample: it multiplies by the weight (a NaN target would reach the loss)."""
+    yy = y.detach().requires_grad_(True)
+    B = y.shape[0]
+    s = w * (B / w.sum())
+    per = (yy - t).abs().mean(dim=(1, 2, 3)) + WEIGHT * (1 - torch_ssim(yy, t, data_range=data_range))
+    loss = (s * per).sum() / B
+    return loss, torch.autograd.grad(loss, yy)[0]
+
+
+def sample_weight_cases(a):
+    cases = []
+    for B, H, W in SW_SHAPES:
+        gen = torch.Generator().manual_seed(43)
+        t = blobs(B, H, W, gen).cuda()
+        y = (t + 0.5 * torch.randn(t.shape, generator=gen).cuda()).clamp_min(0).contiguous()
+        ones = torch.ones(B, device="cuda")
+        half = (torch.randperm(B, generator=gen) < B // 2).float().cuda()      # a random half: no pattern in the index
+        every_2nd = (torch.arange(B, device="cuda") % 2 == 0).float()          # images 1, 3, 5, ... unlabeled
+
+        def hip(w):
+            return Fh.sr_loss_fwd_bwd(y, t, WEIGHT, data_range=10.0, pixel_kind=SW_KIND, sample_weight=w)
+
+        fns = {"unweighted_pair": lambda: hip(None), "weighted_ones": lambda: hip(ones), "weighted_half_zero": lambda: hip(half),
+               "weighted_every_2nd_zero": lambda: hip(every_2nd),
+               "torch_ones": lambda: torch_weighted(y, t, ones, 10.0), "torch_half_zero": lambda: torch_weighted(y, t, half, 10.0)}
+        big = B * H * W > 1 << 22
+        rounds = alternate(fns, a.warmup, a.rounds, max(a.launches // 10, 3) if big else a.launches)
+        med = {k: statistics.median(v) for k, v in rounds.items()}
+        for k, v in rounds.items():
+            against = "torch_ones" if k.endswith("ones") else "torch_half_zero" if k.endswith("zero") else None
+            case = dict(shape=[B, 1, H, W], launch=k, ms_median=round(med[k], 5), ms_spread=round(max(v) - min(v), 5),
+                        rounds_ms=[round(x, 5) for x in v], ratio_to_unweighted_pair=round(med[k] / med["unweighted_pair"], 4))
+            if against and not k.startswith("torch"):
+                case.update(ratio_to_torch=round(med[k] / med[against], 4), slower_than_torch=bool(med[k] > med[against]))
+            cases.append(case)
+            print(f"[loss microbench] sample weight ({B},1,{H},{W}) {k:23s}: {med[k]:9.4f} ms (spread {case['ms_spread']:.4f}), "
+                  f"{case['ratio_to_unweighted_pair']:.3f} x the unweighted pair" +
+                  (f", {case['ratio_to_torch']:.3f} x the torch composition" if "ratio_to_torch" in case else ""), flush=True)
+        del y, t
+        torch.cuda.empty_cache()
+    return cases
+
+
+def sample_weight_step_cases(a):
+    """The B = 32 train step (L1 + SSIM), eager and graph-replayed: a 2-tuple batch, and a 4-tuple with all weights 1 and
+    with a random half of them 0."""
+    cases = []
+    B = 32
+    gen = torch.Generator().manual_seed(43)
+    LR, HR = (torch.rand(B, 3, 4, 4, generator=gen) * 8).cuda(), (blobs(B, 100, 100, gen) * 10).cuda()
+    batches = {"no_weight": (LR, HR), "weights_one": (LR, HR, None, torch.ones(B, device="cuda")),
+               "weights_half_zero": (LR, HR, None, (torch.randperm(B, generator=gen) < B // 2).float().cuda())}
+    for mode in ("eager", "graphed"):
+        fns, models = {}, {}
+        for name, batch in batches.items():
+            m, opt, conf = build(WEIGHT)
+            conf["pixel_loss"] = SW_KIND
+            models[name] = m
+            if mode == "graphed":
+                fns[name] = lambda g=GraphedTrainStep(m, opt, conf, warmup=1), b=batch: g(b)
+            else:
+                fns[name] = lambda m=m, opt=opt, conf=conf, b=batch: TR.train_one_iter(m, opt, b, conf)
+        n = a.steps * 10
+        rounds = alternate(fns, max(a.warmup, 3), a.rounds, n)
+        med = {k: statistics.median(v) for k, v in rounds.items()}
+        run_spread = max(max(v) - min(v) for v in rounds.values())
+        for name, v in rounds.items():
+            with torch.no_grad():
+                models[name].eval()
+                frac = float((models[name](LR[:8].float()) > 0).float().mean())
+                models[name].train()
+            case = dict(B=B, mode=mode, batch=name, ms_per_step_median=round(med[name], 4),
+                        ms_per_step_spread=round(max(v) - min(v), 4), rounds_ms=[round(x, 4) for x in v],
+                        delta_to_no_weight_ms=round(med[name] - med["no_weight"], 4), run_spread_ms=round(run_spread, 4),
+                        steps_per_round=n, out_nonzero_frac=round(frac, 5), valid=bool(frac > 0))
+            cases.append(case)
+            print(f"[loss microbench] sample weight step B={B} {mode:7s} {name:17s}: {med[name]:9.4f} ms/step (spread "
+                  f"{case['ms_per_step_spread']:.4f}), {case['delta_to_no_weight_ms']:+.4f} ms to no weight (run spread "
+                  f"{run_spread:.4f})" + ("" if case["valid"] else "  INVALID: the output is all zero"), flush=True)
+        del fns, models
+        torch.cuda.empty_cache()
+    return cases
+
+
 def build(weight):
     torch.manual_seed(42)
     m = tactilesr_amd.TactileSR().cuda().train()
@@ -376,17 +477,29 @@ def main():
     ap.add_argument("--pixel-loss", action="store_true", help="time the pixel-loss launch instead (see the docstring)")
     ap.add_argument("--degradation", action="store_true", help="time the degradation launch and its step instead (see "
                                                                "the docstring)")
+    ap.add_argument("--sample-weight", action="store_true", help="time the per-sample weight launches and their step instead "
+                                                                 "(see the docstring)")
     ap.add_argument("--out", default=None, help="default: profiles/ssim_loss_cost.json, profiles/pixel_loss_cost.json "
-                                                "with --pixel-loss, profiles/degradation_loss_cost.json with --degradation")
+                                                "with --pixel-loss, profiles/degradation_loss_cost.json with --degradation, "
+                                                "profiles/sample_weight_cost.json with --sample-weight")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "degradation_loss_cost.json" if a.degradation else
+        a.out = os.path.join(REPO, "profiles", "sample_weight_cost.json" if a.sample_weight else
+                             "degradation_loss_cost.json" if a.degradation else
                              "pixel_loss_cost.json" if a.pixel_loss else "ssim_loss_cost.json")
     if not torch.cuda.is_available():
         raise SystemExit("loss_microbench: needs a ROCm device (the timing is of the GPU)")
     result = dict(tool="tools/loss_microbench.py", device=torch.cuda.get_device_name(0), rounds=a.rounds, warmup=a.warmup,
                   launches=a.launches, steps=a.steps, weight=WEIGHT, lr=LR_START)
-    if a.degradation:
+    if a.sample_weight:
+        import datetime
+        result = dict(tool="tools/loss_microbench.py --sample-weight", device=result["device"],
+                      date=datetime.date.today().isoformat(), rounds=a.rounds, warmup=a.warmup, launches=a.launches,
+                      steps=a.steps, ssim_weight=WEIGHT, pixel_loss=SW_KIND, lr=LR_START, norm="sum",
+                      not_measured=["the parent commit's own binary: unweighted_pair and no_weight are this build's "
+                                    "unweighted entry points"],
+                      launch=sample_weight_cases(a), step=sample_weight_step_cases(a))
+    elif a.degradation:
         result = dict(tool="tools/loss_microbench.py --degradation", device=result["device"], rounds=a.rounds,
                       warmup=a.warmup, launches=a.launches, steps=a.steps, weight=WEIGHT, gamma=DEG_GAMMA, gain=DEG_GAIN,
                       lr=LR_START, launch=degradation_cases(a), step=degradation_step_cases(a))
