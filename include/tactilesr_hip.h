@@ -918,6 +918,15 @@ int tsr_sgemm_splitk_strided(const float* A, long long sa0, long long sa1, const
 /* Column sums of Y[M][N] per row range (db = 1^T dy over the same K ranges as the split-K GEMM with K = M):
  * slab[s*split_stride + j] = sum of rows of range s. */
 int tsr_colsum_splitk(const float* Y, float* slab, long long split_stride, int M, int N, int nsplit, void* stream);
+/* Which kernel form a launch of the tsr_sgemm family takes (host arithmetic: no launch, no device call; the launches make
+ * their choice through the same function).  Returns BM*100 + AF*10 + BF: BM = tile height, 64 or 128 (128 unless
+ * ceil(N/128) * ceil(M/128) * nsplit < 384 and M > 64); AF / BF = load path of A / B: 1 = 16-B loads along k (unit stride
+ * along k, the other stride and K multiples of 4, pointer 16-B aligned), else 2 = 16-B loads along m / n (unit stride
+ * along m / n, the other stride and M / N multiples of 4, pointer 16-B aligned), else 0 = scalar loads.  a_align16 /
+ * b_align16: non-zero when the operand's pointer is 16-B aligned.  nsplit = 1 for tsr_sgemm and tsr_sgemm_masked.  Returns 0
+ * for what the launches refuse: M, N or K <= 0, nsplit outside 1..65535. */
+int tsr_sgemm_form(long long sa0, long long sa1, long long sb0, long long sb1, int a_align16, int b_align16,
+                   int M, int N, int K, int nsplit);
 /* dy *= act'(.) in place from the stored activation output (1 ReLU, 2 Softplus). */
 int tsr_act_bwd(float* dy, const float* y, long long n, int mode, void* stream);
 

@@ -123,6 +123,7 @@ SIGNATURES = {
     "tsr_sgemm_masked": [_P, _L, _L, _P, _L, _L, _P, _P, _I, _I, _I, _P],
     "tsr_sgemm_splitk_strided": [_P, _L, _L, _P, _L, _L, _P, _L, _I, _I, _I, _I, _P],
     "tsr_colsum_splitk": [_P, _P, _L, _I, _I, _I, _P],
+    "tsr_sgemm_form": [_L, _L, _L, _L, _I, _I, _I, _I, _I, _I],
     "tsr_act_bwd": [_P, _P, _L, _I, _P],
     "tsr_nchw_to_cb16": [_P, _P, _I, _I, _I, _I, _I, _P],
     "tsr_cb16_to_nchw": [_P, _P, _I, _I, _I, _I, _I, _P],

@@ -218,18 +218,32 @@ static void sgemm_launch_a(const SgemmArgs& g, int af, int bf, dim3 grid, hipStr
 
 static bool al16(const void* p) { return (((size_t)p) & 15) == 0; }
 
-static int sgemm_dispatch(SgemmArgs g, int nsplit, hipStream_t st) {
+// The launch form of one GEMM: BM * 100 + AF * 10 + BF (host arithmetic; the launch path and tsr_sgemm_form share it)
+static int sgemm_form(long sa0, long sa1, long sb0, long sb1, bool a16, bool b16, int M, int N, int K, int nsplit) {
   // which dimension of each operand is 16-B loadable: the unit-stride one, with the other stride a multiple of 4 floats
   // (and the vectorised extent itself a multiple of 4: the four elements of a 16-B item are then in range together)
-  const int af = (g.sa1 == 1 && (g.sa0 & 3) == 0 && (g.K & 3) == 0 && al16(g.A)) ? 1
-               : ((g.sa0 == 1 && (g.sa1 & 3) == 0 && (g.M & 3) == 0 && al16(g.A)) ? 2 : 0);
-  const int bf = (g.sb0 == 1 && (g.sb1 & 3) == 0 && (g.K & 3) == 0 && al16(g.B)) ? 1
-               : ((g.sb1 == 1 && (g.sb0 & 3) == 0 && (g.N & 3) == 0 && al16(g.B)) ? 2 : 0);
-  const int nx = (g.N + SG_BN - 1) / SG_BN;
+  const int af = (sa1 == 1 && (sa0 & 3) == 0 && (K & 3) == 0 && a16) ? 1
+               : ((sa0 == 1 && (sa1 & 3) == 0 && (M & 3) == 0 && a16) ? 2 : 0);
+  const int bf = (sb0 == 1 && (sb1 & 3) == 0 && (K & 3) == 0 && b16) ? 1
+               : ((sb1 == 1 && (sb0 & 3) == 0 && (N & 3) == 0 && b16) ? 2 : 0);
+  const int nx = (N + SG_BN - 1) / SG_BN;
   // 128-row tiles unless they leave the chip less than half full and 64-row tiles do better
-  const long wg128 = (long)nx * ((g.M + 127) / 128) * nsplit;
-  const bool small = wg128 < 384 && g.M > 64;
-  if (small) {
+  const long wg128 = (long)nx * ((M + 127) / 128) * nsplit;
+  const bool small = wg128 < 384 && M > 64;
+  return (small ? 64 : 128) * 100 + af * 10 + bf;
+}
+
+extern "C" int tsr_sgemm_form(long long sa0, long long sa1, long long sb0, long long sb1, int a_align16, int b_align16,
+                              int M, int N, int K, int nsplit) {
+  if (M <= 0 || N <= 0 || K <= 0 || nsplit <= 0 || nsplit > 65535) return 0;
+  return sgemm_form((long)sa0, (long)sa1, (long)sb0, (long)sb1, a_align16 != 0, b_align16 != 0, M, N, K, nsplit);
+}
+
+static int sgemm_dispatch(SgemmArgs g, int nsplit, hipStream_t st) {
+  const int form = sgemm_form(g.sa0, g.sa1, g.sb0, g.sb1, al16(g.A), al16(g.B), g.M, g.N, g.K, nsplit);
+  const int af = form / 10 % 10, bf = form % 10;
+  const int nx = (g.N + SG_BN - 1) / SG_BN;
+  if (form / 100 == 64) {
     dim3 grid(nx, (g.M + 63) / 64, nsplit);
     sgemm_launch_a<64>(g, af, bf, grid, st);
   } else {

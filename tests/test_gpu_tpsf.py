@@ -170,8 +170,10 @@ def test_dataset_generator_matches_batch1_loop(tmp_path):
 @pytest.mark.parametrize("M,N,K,act,ta,tb", [
     (37, 3, 256, 2, False, True), (130, 256, 48, 1, False, True), (64, 64, 16, 0, False, False),
     (100, 70, 33, 0, True, False), (1, 129, 300, 0, False, False), (257, 65, 1030, 1, True, True),
-    # the MLP's own shapes at a batch that runs whole 128-row tiles and the 16-B load paths: forward (k-fast x k-fast),
-    # dx (k-fast x n-fast), dW (m-fast x n-fast, K = batch), and ragged edges on every path
+    # the MLP's own shapes on the 16-B load paths: forward (k-fast x k-fast), dx (k-fast x n-fast), dW (m-fast x n-fast,
+    # K = batch), and ragged edges on every path.  By tsr_sgemm_form these run 64-row tiles (M > 64 takes 128-row tiles only
+    # from 384 workgroups on) or 128-row tiles with M <= 64; rows in the upper half of a 128-row tile, and all 18 forms,
+    # are in tests/test_gpu_sgemm.py
     (640, 1024, 256, 1, False, True), (600, 256, 1024, 0, False, False), (1024, 256, 2048, 0, True, False),
     (3, 256, 2048, 0, True, False), (515, 260, 132, 2, False, True), (260, 516, 1028, 0, True, False),
 ])
