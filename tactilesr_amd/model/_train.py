@@ -542,7 +542,13 @@ class TrainEngine:
         sf, T, A = m.scale_factor, m.seqsCnt, m.axisCnt
         H, W = hin * sf, win * sf
         HW = H * W
-        check_trainable_size(H, W)          # before any launch: a refused step leaves parameters and statistics as they were
+        # every refusal comes before the first launch: a refused step leaves parameters and statistics as they were
+        m._check_input(x)
+        check_trainable_size(H, W)
+        if len(m.patternFeatureExtra_layer) == 0:
+            raise _lib.TactileSRHipError("train path needs patternFeatureExtraLayerCnt >= 1")
+        if len(m.forceFeatureExtra_layer) == 0:
+            raise _lib.TactileSRHipError("train path needs forceFeatureExtraLayerCnt >= 1")
         c = self._new_ctx(B, H, W, dev)
         c.x, c.hin, c.win = x.detach(), hin, win
         c.want_dx = False        # TrainFn sets it when the taxels require grad: backward then also leaves c.dx
@@ -594,8 +600,6 @@ class TrainEngine:
             s = self._msrb_fwd(c, blk, X, out, octot, ocoff, am_o, new_amax, buf)
             X = s.Y
             c.blocks.append(s)
-        if n_msrb == 0:
-            raise _lib.TactileSRHipError("train path needs patternFeatureExtraLayerCnt >= 1")
         # ---- force branch
         c.f0 = buf(64)
         am_f0 = new_amax()
@@ -603,8 +607,6 @@ class TrainEngine:
         F0 = Act(c.f0, 64, 0, 64, amax=am_f0)
         c.res = []
         n_res = len(m.forceFeatureExtra_layer)
-        if n_res == 0:
-            raise _lib.TactileSRHipError("train path needs forceFeatureExtraLayerCnt >= 1")
         for i, rb in enumerate(m.forceFeatureExtra_layer):
             if i == n_res - 1:
                 out, octot, ocoff, am_o = c.hcat, 128, 0, c.am_hcat

@@ -521,7 +521,10 @@ class TactileSR(_PlanCache, nn.Module):
 
     ``model(LR)`` with LR ``(B, seqsCnt*axisCnt, 4, 4)`` fp32 on a ROCm device returns
     ``(B, 1, 4*scale_factor, 4*scale_factor)``, numerically equal (<=1e-5 relative) to
-    the reference forward (model/tactileSR_model.py:67-84).
+    the reference forward (model/tactileSR_model.py:67-84).  Any other taxel grid and ``axisCnt != 3`` are refused
+    before the first launch: the reference resizes its output to ``(4*scale_factor, 4*scale_factor)`` whatever the
+    grid, and the stem kernels are 3-axis.  ``seqsCnt`` and the two block counts are free (a count of 0 copies that
+    branch's input into the head's input; the train step and the bf16-storage path need both counts >= 1).
     """
     _plan_fields = ("conv_impl", "head_impl", "fuse_1x1", "fuse_pair")
 
@@ -664,6 +667,8 @@ class TactileSR(_PlanCache, nn.Module):
         if n_msrb == 0:
             call("tsr_cb16_to_nchw", ptr(xa), ptr(xb), _I(B), _I(64), _I(HW), _I(64), _I(0), stream())
             call("tsr_nchw_to_cb16", ptr(xb), ptr(hcat), _I(B), _I(64), _I(HW), _I(128), _I(64), stream())
+            if s_hcat is not None:    # the copy has no epilogue to raise the slot: hcat's bound must cover the copied half
+                torch.maximum(s_hcat, s_x, out=s_hcat)
         cur, nxt = xa, xb
         for i, p in enumerate(plan["msrb"]):
             if i == n_msrb - 1:   # pattern feature lands in channels [64,128) of the head input (cat: force first)
@@ -685,6 +690,8 @@ class TactileSR(_PlanCache, nn.Module):
         if n_res == 0:
             call("tsr_cb16_to_nchw", ptr(f0), ptr(f1), _I(B), _I(64), _I(HW), _I(64), _I(0), stream())
             call("tsr_nchw_to_cb16", ptr(f1), ptr(hcat), _I(B), _I(64), _I(HW), _I(128), _I(0), stream())
+            if s_hcat is not None:
+                torch.maximum(s_hcat, s_f, out=s_hcat)
         cur, nxt = f0, (buf(64) if n_res > 1 else None)
         for i, p in enumerate(plan["res"]):
             if i == n_res - 1:
@@ -692,6 +699,8 @@ class TactileSR(_PlanCache, nn.Module):
             else:
                 dst, s_out = (nxt, 64, 0), slot()
             _run_res(p, prof, cur, s_f, *dst, s_out, f1, slot, B, H, W)
+            if stages is not None and i < n_res - 1:      # (the last block's output is the stage "force")
+                stages[f"res{i}"] = (dst[0].clone(),) + dst[1:]
             cur, nxt, s_f = nxt, cur, s_out
         h0 = buf(128)
         _conv(prof, plan["head0"], hcat, 128, 0, h0, 128, 0, True, B, H, W, amax_in=s_hcat, amax_out=None)
@@ -701,8 +710,22 @@ class TactileSR(_PlanCache, nn.Module):
         call(*_twin_args(io16, "tsr_head_fwd", (ptr(h0), _I(128), _I(128), ptr(plan["head_w"]), ptr(out), _I(1), _I(B), _I(H),
                                                 _I(W))), stream())
 
-    def forward(self, x):
+    def _check_input(self, x):
+        """What every forward (eval, train, `forward_with_stages`) refuses before its first launch: anything the
+        reference's forward does not compute as this engine would."""
         assert x.shape[1] == self.seqsCnt * self.axisCnt, "input channel should be same with seqsCnt x axisCnt!"
+        if self.axisCnt != 3:
+            raise _lib.TactileSRHipError(f"TactileSR: axisCnt = {self.axisCnt} is not available: the stem kernels (pattern "
+                                         "and force stems, their weight and taxel gradients) are written for 3-axis taxels")
+        n = self.taxel_cnt
+        if x.dim() != 4 or tuple(x.shape[2:]) != (n, n):
+            raise _lib.TactileSRHipError(
+                f"TactileSR: taxel grid {tuple(x.shape[2:])} is not available, only {n} x {n}: the reference ends with a "
+                f"fixed output resize to ({n}*scale_factor, {n}*scale_factor) (model/tactileSR_model.py:83), an identity "
+                f"on {n} x {n} taxels only; this engine has no such resize and would return another image")
+
+    def forward(self, x):
+        self._check_input(x)
         if not x.is_cuda:
             raise _lib.TactileSRHipError("TactileSR (tactilesr_amd) runs on MI355X only: move the model and "
                                          "its input to a ROCm device (no CPU fallback)")
@@ -752,6 +775,7 @@ class TactileSR(_PlanCache, nn.Module):
         """Eval forward that also returns named intermediate activations converted to
         NCHW (parity probes against the oracle's ``stages``)."""
         assert not self.training
+        self._check_input(x)
         x = x.detach().float().contiguous()
         B = x.shape[0]
         H, W = x.shape[2] * self.scale_factor, x.shape[3] * self.scale_factor
