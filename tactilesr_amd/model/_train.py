@@ -999,6 +999,12 @@ class TrainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         c = ctx.c
+        if c is None:
+            # the first backward released the forward's context (activations, BatchNorm vectors: device memory of the size
+            # of the step) -- a second pass over the same graph has nothing to differentiate
+            raise _lib.TactileSRHipError(
+                "second backward through the same tactilesr_amd forward: the first backward released the saved "
+                "activations (retain_graph=True does not keep them); run the forward again for another backward")
         grads = ctx.engine.backward(c, dout)
         dx, c.dx = c.dx, None
         ctx.c = None

@@ -4,31 +4,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _block_cases import block_data, device_masks, make_block, oracle_block, randomise as _randomise, relerr
 from oracle import tactilesr_oracle as O
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-
-
-def relerr(a, b):
-    a, b = a.detach().cpu().double(), b.detach().cpu().double()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
-
-
-def _randomise(block, seed):
-    """Trained-like parameters: random BN affine / running statistics, biases (the seeded init has gamma = beta = 0.1)."""
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for k, v in block.state_dict().items():
-            if k.endswith("running_var"):
-                v.copy_(torch.rand(v.shape, generator=g) + 0.5)
-            elif k.endswith("running_mean"):
-                v.copy_(torch.randn(v.shape, generator=g) * 0.2)
-            elif k.endswith(".1.weight"):
-                v.copy_(torch.rand(v.shape, generator=g) + 0.5)
-            elif k.endswith("bias"):
-                v.copy_(torch.randn(v.shape, generator=g) * 0.1)
-    return {k: v.detach().clone() for k, v in block.state_dict().items()}
 
 
 @pytest.mark.parametrize("impl", ["fp16x3", "f32", "bf16x6"])
@@ -93,14 +73,10 @@ def test_standalone_msrb_runs_the_network_block_code(impl):
 def _block_train_check(kind, B, H, W, seed):
     """Train-mode forward (batch statistics, running-stat update) and backward (input + every parameter) of a standalone
     block against torch autograd on the CPU oracle in fp64, gradients evaluated on the device's own ReLU pattern
-    (tests/_gradcheck.py explains the split); bars as for the whole network: output / loss 1e-5, gradients 2e-5."""
-    import tactilesr_amd
-    torch.manual_seed(seed)
-    blk = tactilesr_amd.MSRB() if kind == "msrb" else tactilesr_amd.ResBlock()
-    sd = _randomise(blk, seed + 1)
-    g = torch.Generator().manual_seed(seed + 2)
-    x = torch.randn(B, 64, H, W, generator=g).clamp_(min=0) * 2 + 0.01 * torch.randn(B, 64, H, W, generator=g)
-    dy = torch.randn(B, 64, H, W, generator=g)
+    (tests/_gradcheck.py explains the split); bars as for the whole network: output / loss 1e-5, gradients 2e-5.  Data and
+    the oracle half live in tests/_block_cases.py (`legacy` law); tests/test_gpu_block_cases.py runs the full table."""
+    blk, sd = make_block(kind, seed)
+    x, dy = block_data(kind, B, H, W, seed=seed, legacy=True)
     blk = blk.cuda().train()
     eng = blk.block_engine()
     eng.keep_ctx = True
@@ -108,40 +84,15 @@ def _block_train_check(kind, B, H, W, seed):
     y = blk(xg)
     (y * dy.cuda()).sum().backward()
     # device ReLU pattern of this forward -> oracle masks
-    c = eng.last_ctx
-    from tactilesr_amd.model.tactileSR_model import from_cb16
-    s = c.s
-    masks = {}
-
-    def bn_mask(buf, ctot, coff, C, scale, shift):
-        z = from_cb16(buf, B, C, H, W, ctot, coff).double().cpu()
-        return (z * scale.double().cpu().view(1, -1, 1, 1) + shift.double().cpu().view(1, -1, 1, 1)) > 0
-
-    if kind == "msrb":
-        masks["b.conv_3_1.1"] = bn_mask(s.cat1, 128, 0, 64, s.bn_c1[0, :64], s.bn_c1[1, :64])
-        masks["b.conv_5_1.1"] = bn_mask(s.cat1, 128, 64, 64, s.bn_c1[0, 64:], s.bn_c1[1, 64:])
-        masks["b.conv_3_2.1"] = bn_mask(s.cat2, 256, 0, 128, s.bn_c2[0, :128], s.bn_c2[1, :128])
-        masks["b.conv_5_2.1"] = bn_mask(s.cat2, 256, 128, 128, s.bn_c2[0, 128:], s.bn_c2[1, 128:])
-    else:
-        masks["b.conv1"] = from_cb16(s.F1.buf, B, 64, H, W).cpu() > 0
-    masks["b.out"] = y.detach().cpu() > 0
-    p64 = {f"b.{k}": (v.double().requires_grad_(O.is_trainable(k)) if v.is_floating_point() else v) for k, v in sd.items()}
-    x64 = x.double().requires_grad_(True)
-    ns = {}
-    tap = O.ReluTap(masks=masks)
-    if kind == "msrb":
-        ref = O.msrb_forward(p64, "b", x64, training=True, new_stats=ns, tap=tap)
-    else:
-        ref = O.resblock_forward(p64, "b", x64, tap=tap)
-    leaves = [v for k, v in p64.items() if v.is_floating_point() and v.requires_grad]
-    names = [k for k, v in p64.items() if v.is_floating_point() and v.requires_grad]
-    grads = torch.autograd.grad((ref * dy.double()).sum(), [x64] + leaves)
+    masks = device_masks(kind, eng.last_ctx.s, y, B, H, W)
+    r = oracle_block(kind, sd, x, dy, masks=masks)
+    ref = r.out
     assert relerr(y, ref) < TOL
-    assert relerr(xg.grad, grads[0]) < 2e-5
+    assert relerr(xg.grad, r.dx) < 2e-5
     named = dict(blk.named_parameters())
     worst = 0.0
-    for n, gr in zip(names, grads[1:]):
-        got = named[n[2:]].grad
+    for n, gr in r.grads.items():
+        got = named[n].grad
         assert got is not None, n
         if float(gr.abs().max()) < 1e-9 * float(dy.abs().max()) * B * H * W:      # conv bias in front of a train-mode BN
             assert float(got.abs().max()) < 1e-3, n
@@ -150,10 +101,10 @@ def _block_train_check(kind, B, H, W, seed):
         worst = max(worst, e)
         assert e < 2e-5, (n, e)
     new_sd = blk.state_dict()
-    for k, v in ns.items():
+    for k, v in r.ns.items():
         if k.endswith("running_mean") or k.endswith("running_var"):
-            assert relerr(new_sd[k[2:]], v) < TOL, k
-    print(f"[standalone {kind} train] out {relerr(y, ref):.2e}, dx {relerr(xg.grad, grads[0]):.2e}, worst param grad {worst:.2e}")
+            assert relerr(new_sd[k], v) < TOL, k
+    print(f"[standalone {kind} train] out {relerr(y, ref):.2e}, dx {relerr(xg.grad, r.dx):.2e}, worst param grad {worst:.2e}")
     # no-grad train-mode call: forward only, statistics still move
     with torch.no_grad():
         y2 = blk(x.cuda())
