@@ -1,8 +1,8 @@
 // fp16x3 implicit-GEMM convolution on v_mfma_f32_16x16x32_f16 (K = 32 per instruction), the default form of the
 // 3x3 / 5x5 convolutions.  Same arithmetic as conv_mfma_split16.hip (fp32 operands as two power-of-two-scaled fp16
 // planes, products h2g1 + h1g1 + h1g2 accumulated in fp32), same halo staging (slab split on the fly), same 3-slot weight
-// ring (fed by LDS-DMA in the inference instantiations, through registers in the training ones), same epilogues -- a
-// different matrix instruction:
+// ring (fed by LDS-DMA in the inference instantiations -- in the 5x5 ones piece by piece behind the first MFMA rows of a
+// step, see DMA_BYTES -- through registers in the training ones), same epilogues -- a different matrix instruction:
 //
 //   * Why: under an MFMA-dense loop the MI355X lowers its clock, and it holds a HIGHER clock on the 16x16x32 shape than
 //     on 32x32x16 at equal cycles per FLOP (MI355X_MICROARCH.md, DVFS give-back item 7).  Measured on this kernel's
@@ -167,7 +167,10 @@ __global__ __launch_bounds__(NTHR, NTHR == 512 ? 1 : 2) void conv_k32_kernel(con
   const int nchunk = nreal + (nreal & 1);     // blocks come in pairs
   const int S = (nchunk >> 1) * T;            // steps: HS per even block, HS + 1 per odd block
   const char* wsrc = (const char*)a.wp;
-  const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.wp, 0, 0x7fffffff, 0x00020000);
+  // The descriptor covers exactly the stream: the requests of the last two steps (slabs S, S + 1) fall outside it and
+  // the buffer range check drops them, so the step body carries no branch around its requests.
+  const int wbytes = !WDMA ? 0x7fffffff : PAIR ? (nchunk >> 1) * ((2 * 65536 + 8192) * 2) : S * WSLAB_B;
+  const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.wp, 0, wbytes, 0x00020000);
 
   // BN scale / shift of this thread's channel quad of the block in flight (every staging item of a thread carries the
   // same quad): requested WITH the slab, not at the block boundary where the conversion would wait for them
@@ -213,8 +216,18 @@ __global__ __launch_bounds__(NTHR, NTHR == 512 ? 1 : 2) void conv_k32_kernel(con
     }
   };
   // Weight slabs travel global memory -> LDS by LDS-DMA (global_load_lds_dwordx4: 1 KB per wave instruction, no VGPR hop,
-  // no ds_write): slab s+2 is requested at the START of step s into ring slot (s+2)%3 -- free since the barrier that ended
-  // step s-1 -- and awaited (vmcnt 0) before the barrier that ends step s, which publishes it.  The instruction is the
+  // no ds_write): slab s+2 is requested DURING step s into ring slot (s+2)%3 -- free since the barrier that ended
+  // step s-1 -- and awaited (vmcnt 0) before the barrier that ends step s, which publishes it.
+  // Order of the vector-memory operations of a step (vmcnt counts in issue order):
+  //   * 5x5 plain / fused (WROWS): [the next block's halo loads, in the step that has them] first, then the slab's pieces,
+  //     hi plane first, one behind each of the first WV MFMA rows of P0 (each row fenced with sched_barrier, so the piece
+  //     stays behind the row's MFMAs and fragment reads), nothing after them: the wait in front of the barrier is vmcnt(0).
+  //     With all pieces at the top of the step a wave spends ~210 cycles issuing them between the barrier and its first
+  //     MFMA (stamped: 42 cycles per piece -- cheap, but serial); behind the rows they issue under the MFMAs.  The last two
+  //     steps request slabs S, S + 1: past the end of the buffer descriptor, dropped by its range check (no branch).
+  //   * 3x3 (DBH) and pair: all pieces at the top of the step, THEN the halo loads of the step, and the counted wait
+  //     DMA_WAIT_N(NIT) that leaves those NIT youngest operations in flight (no gain measured from the row placement).
+  // The instruction is the
   // MUBUF form (buffer_load_dwordx4 ... lds), not global_load_lds: hipcc models the FLAT-encoded one as a possible LDS
   // access through FLAT and then degrades every counted lgkmcnt wait of the step to lgkmcnt(0) -- a full LDS drain in the
   // middle of every step (whole eval forward 133.3 -> 131.9 ms with the MUBUF form).  Against register staging
@@ -228,6 +241,10 @@ __global__ __launch_bounds__(NTHR, NTHR == 512 ? 1 : 2) void conv_k32_kernel(con
       __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (__attribute__((address_space(3))) void*)(dst_ + v * NTHR * 16), 16, \
                                                vo_ + v * NTHR * 16, 0, 0, 0);             \
   }
+  // one 1 KB piece (v_ of the slab's WV, or WV / 2) of the slab whose lane offset in the stream is vo_
+#define DMA_PIECE(vo_, slot_, v_)                                                        \
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (__attribute__((address_space(3))) void*)(wbuf + (slot_) * WSLAB_B + wave_s * 1024 + (v_) * NTHR * 16), \
+                                           16, (vo_) + (v_) * NTHR * 16, 0, 0, 0)
   // Training launches (EXT) keep REGISTER staging -- slab s+3 loaded into VGPRs at the end of step s, written to LDS at
   // the end of step s+1 -- and 512-thread workgroups: same-box A/B of the train step 277.2 ms against 281.7 (LDS-DMA, 256
   // threads) / 285 (LDS-DMA, 512 threads); the inference launches gain 4 % from LDS-DMA at 256 threads (138.5 -> 132.8 ms).
@@ -256,31 +273,40 @@ __global__ __launch_bounds__(NTHR, NTHR == 512 ? 1 : 2) void conv_k32_kernel(con
   }
 #define STEP_BARRIER() __syncthreads()
   // fragments of pair step st_ (taps 2 st_, 2 st_ + 1 of the resident block), plane p_
-#define LOAD_A(dst, p_, st_, hb_)                                                        \
+  // (the _1 forms read one m-tile / n-tile: the inference steps place every read behind the MFMAs it follows in issue)
+#define LOAD_A_1(dst, p_, st_, hb_, mt_)                                                 \
   {                                                                                      \
     const int kh_ = PAIR ? PAIR_KH[(st_)] : (2 * (st_)) / KS, kw_ = PAIR ? PAIR_KW[(st_)] : (2 * (st_)) - kh_ * KS; \
     const bool x_ = PAIR ? PAIR_V[(st_)] == 0 : kw_ < KS - 1;                            \
     const char* ab_ = lds + (x_ ? lx : lw) + (hb_) * HALO_B + kh_ * ROWB + kw_ * PIXB + (p_) * 32; \
-    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) dst[mt] = *(const kf16x8*)(ab_ + mt * 2 * ROWB); \
+    dst[(mt_)] = *(const kf16x8*)(ab_ + (mt_) * 2 * ROWB);                               \
   }
+#define LOAD_A(dst, p_, st_, hb_)                                                        \
+  {                                                                                      \
+    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) LOAD_A_1(dst, p_, st_, hb_, mt);    \
+  }
+#define LOAD_A_CROSS_1(dst, p_, mt_) dst[(mt_)] = *(const kf16x8*)(lds + lc + (mt_) * lcs + (p_) * 32)
 #define LOAD_A_CROSS(dst, p_)                                                            \
   {                                                                                      \
-    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) dst[mt] = *(const kf16x8*)(lds + lc + mt * lcs + (p_) * 32); \
+    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) LOAD_A_CROSS_1(dst, p_, mt);        \
   }
+#define LOAD_A_CROSSD_1(dst, p_, mt_) dst[(mt_)] = *(const kf16x8*)(lds + lcd + (mt_) * 2 * ROWB + (p_) * 32)
 #define LOAD_A_CROSSD(dst, p_)                                                           \
   {                                                                                      \
-    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) dst[mt] = *(const kf16x8*)(lds + lcd + mt * 2 * ROWB + (p_) * 32); \
+    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) LOAD_A_CROSSD_1(dst, p_, mt);       \
   }
+#define LOAD_B_1(dst, p_, slot_, nt_)                                                    \
+  dst[(nt_)] = *(const kf16x8*)(wbuf + (slot_) * WSLAB_B + laneB + (p_) * (2 * COUT * 16) + (nt_) * 256)
 #define LOAD_B(dst, p_, slot_)                                                           \
   {                                                                                      \
-    const char* wb_ = wbuf + (slot_) * WSLAB_B + laneB + (p_) * (2 * COUT * 16);         \
-    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) dst[nt] = *(const kf16x8*)(wb_ + nt * 256); \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) LOAD_B_1(dst, p_, slot_, nt);      \
   }
   // pair form, outer-ring steps: only n-tiles 2, 3 (the 5x5 conv's channels of this wave)
+#define LOAD_B_HI_1(dst, p_, slot_, nt_)                                                 \
+  dst[(nt_)] = *(const kf16x8*)(wbuf + (slot_) * WSLAB_B + laneBh + (p_) * (2 * 64 * 16) + ((nt_) - 2) * 256)
 #define LOAD_B_HI(dst, p_, slot_)                                                        \
   {                                                                                      \
-    const char* wb_ = wbuf + (slot_) * WSLAB_B + laneBh + (p_) * (2 * 64 * 16);          \
-    _Pragma("unroll") for (int nt = 2; nt < NT; ++nt) dst[nt] = *(const kf16x8*)(wb_ + (nt - 2) * 256); \
+    _Pragma("unroll") for (int nt = 2; nt < NT; ++nt) LOAD_B_HI_1(dst, p_, slot_, nt);   \
   }
 #define MFMA_PHASE_HI(A_, B_)                                                            \
   _Pragma("unroll") for (int mt = 0; mt < 4; ++mt)                                       \
@@ -296,6 +322,33 @@ __global__ __launch_bounds__(NTHR, NTHR == 512 ? 1 : 2) void conv_k32_kernel(con
     __builtin_amdgcn_sched_group_barrier(0x008, (per_), 0);                              \
     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                   \
   }
+
+  // one m-tile's MFMAs of a phase
+#define MFMA_ROW(A_, B_, mt_, nt0_)                                                      \
+  _Pragma("unroll") for (int nt = (nt0_); nt < NT; ++nt)                                 \
+    acc[(mt_)][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A_[(mt_)], B_[nt], acc[(mt_)][nt], 0, 0, 0);
+  // hint for one row: nm_ MFMAs (a literal) with nr_ LDS reads spread among them, then pc_ weight-ring pieces (0x040: a
+  // vector-memory operation that writes -- the LDS-DMA request, not a halo load)
+#define HINT_ROW(nm_, nr_, pc_)                                                          \
+  {                                                                                      \
+    if ((nr_) == 2) {                                                                    \
+      __builtin_amdgcn_sched_group_barrier(0x008, (nm_) / 2, 0);                         \
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                 \
+      __builtin_amdgcn_sched_group_barrier(0x008, (nm_) - (nm_) / 2, 0);                 \
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                 \
+    } else if ((nr_) == 1) {                                                             \
+      __builtin_amdgcn_sched_group_barrier(0x008, (nm_), 0);                             \
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                 \
+    } else {                                                                             \
+      __builtin_amdgcn_sched_group_barrier(0x008, (nm_), 0);                             \
+    }                                                                                    \
+    if (pc_) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);                          \
+    __builtin_amdgcn_sched_barrier(0);                                                   \
+  }
+  // The 5x5 inference launches issue the requests of slab s+2 one piece behind each of the first MFMA rows of the step;
+  // the 3x3 (DBH) and pair forms measured no gain from it and keep all pieces at the top of the step
+  constexpr bool WROWS = WDMA && KS == 5 && !PAIR;
+#define PIECE_AT(g_) if ((g_) < WV) DMA_PIECE(vo, slot2, (g_))
 
   // ---- prologue: halo(0), W(0), W(1) in LDS; W(2) in flight
   // power-of-two operand scales (see conv_mfma_split16.hip).  Called AFTER the first slab's global loads have been
@@ -384,7 +437,57 @@ __global__ __launch_bounds__(NTHR, NTHR == 512 ? 1 : 2) void conv_k32_kernel(con
       const int slot2 = slot1 == 2 ? 0 : slot1 + 1;
       const bool cross = ODD && st == HS;
       f32x4 sidev[SCI];
-      if (WDMA && s + 2 < S) {                                     // slab s+2 -> the slot last read a barrier ago
+      if constexpr (WROWS) {
+        // slab s+2 -> the slot last read a barrier ago: one piece behind each of the first WV rows of P0, hi plane first
+        const int vo = (s + 2) * WSLAB_B + tid * 16;
+        if (st == NST - 2 && c + 1 < nchunk) load_halo(c + 1, hv);   // next block's slab: older than every piece of the step
+        // P0: h2 g1; this step's second-phase operands (A0, then B1) are read behind its rows
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+          MFMA_ROW(A1, B0, mt, 0);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (mt >= 2) { LOAD_B_1(B1, 1, slot, 2 * (mt - 2) + h); }
+            else if (cross) { LOAD_A_CROSS_1(A0, 0, 2 * mt + h); }
+            else { LOAD_A_1(A0, 0, st, 0, 2 * mt + h); }
+          }
+          PIECE_AT(mt);
+          HINT_ROW(4, 2, mt < WV);
+        }
+        if (!ODD && st == 0) {
+#pragma unroll
+          for (int k = 0; k < SCI; ++k) sidev[k] = *(const f32x4*)(lds + sc_src + k * SCS * IMGB);
+          __builtin_amdgcn_sched_group_barrier(0x100, SCI, 0);
+        }
+        // P1: h1 g1, with the next step's A1 (same block: the slab is resident)
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+          MFMA_ROW(A0, B0, mt, 0);
+          if (st + 1 < NST) {
+            if (ODD && st + 1 == HS) { LOAD_A_CROSS_1(A1, 1, mt); } else { LOAD_A_1(A1, 1, st + 1, 0, mt); }
+          }
+          HINT_ROW(4, st + 1 < NST ? 1 : 0, false);
+        }
+        // P2: h1 g2, with the next step's B0: published one barrier ago (after the last step: stale, unused)
+        LOAD_B(B0, 0, slot1);
+        MFMA_PHASE(A0, B1);
+        INTERLEAVE(4, 4);
+        if (!ODD && st == 0) {
+#pragma unroll
+          for (int k = 0; k < SCI; ++k) *(f32x4*)(lds + sc_dst + k * SCS * SIMGB) = sidev[k];
+        }
+        DMA_WAIT();                // everything: the halo loads of the step are OLDER than its pieces
+        STEP_BARRIER();
+        if (st + 1 == NST && c + 1 < nchunk) {
+          store_halo(hv, c + 1);     // every wave is past its last read of the old slab (barrier above)
+          __syncthreads();
+          LOAD_A(A1, 1, 0, 0);
+        }
+        ++s;
+        slot = slot1;
+        continue;
+      }
+      if (WDMA && s + 2 < S) {                                    // slab s+2 -> the slot last read a barrier ago
         if constexpr (PAIR) { DMA_WP(slot2, (ODD * HS + st + 2) % 25); } else { DMA_W(s + 2, slot2); }
       }
       const bool outer = PAIR && st < PAIR_OUTER;                  // half-work step: the 5x5 conv's n-tiles only
@@ -503,6 +606,15 @@ __global__ __launch_bounds__(NTHR, NTHR == 512 ? 1 : 2) void conv_k32_kernel(con
 #undef MFMA_PHASE_HI
 #undef MFMA_PHASE
 #undef INTERLEAVE
+#undef MFMA_ROW
+#undef HINT_ROW
+#undef PIECE_AT
+#undef DMA_PIECE
+#undef LOAD_A_1
+#undef LOAD_A_CROSS_1
+#undef LOAD_A_CROSSD_1
+#undef LOAD_B_1
+#undef LOAD_B_HI_1
 
   if constexpr (FUSE2) conv_fuse1x1_epilogue16<IMG>(a, acc, lds, b0, y0, x0, wm, wn, lane, HW, accmul);
   else conv_epilogue16<COUT, EXT, WN>(a, acc, ebase, b0, y0, x0, wm, wn, lane, HW, accmul);
