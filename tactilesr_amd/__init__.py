@@ -9,4 +9,14 @@ from .model.tactileSR_model import TactileSR, TactileSRCNN, MSRB, ResBlock  # no
 from .model.tPSFNet import tPSFNet  # noqa: F401
 from .ema import WeightEMA, recalibrate_bn  # noqa: F401
 
-__all__ = ["TactileSR", "TactileSRCNN", "MSRB", "ResBlock", "tPSFNet", "WeightEMA", "recalibrate_bn"]
+
+def invalidate_weight_packs() -> None:
+    """Drop every cached weight pack and eval plan of every module of this package: the next eval forward packs again.
+    Call it after a write the caches cannot see -- an in-place edit through ``.data`` (``p.data.mul_(2)``,
+    ``p.data.clamp_(..)``) leaves both the tensor's address and its version counter as they were.  Every other writer
+    (in-place under ``no_grad``, ``load_state_dict``, optimizers, ``WeightEMA``, the train step) is seen without it."""
+    _lib.bump_param_epoch()
+
+
+__all__ = ["TactileSR", "TactileSRCNN", "MSRB", "ResBlock", "tPSFNet", "WeightEMA", "recalibrate_bn",
+           "invalidate_weight_packs"]

@@ -69,12 +69,43 @@ def _reapply_hold(root: nn.Module) -> None:
 
 class _PlanCache:
     """Repack when a parameter changed: `_get_plan()` is the class's `_build_plan()`, built again whenever one of its
-    `_plan_fields` attributes, a parameter or a buffer (address or version) or the library's parameter epoch has moved."""
+    `_plan_fields` attributes, a parameter or a buffer (address or version), the `eps` of a BatchNorm layer (the fold bakes
+    it into scale / shift), the library's parameter epoch or the module's own `_plan_gen` (`.half()` / `.float()` / `.to()`)
+    has moved.
+
+    The rule for writers: anything that bumps the tensor's version counter or replaces the tensor is seen -- in-place ops
+    under ``no_grad``, ``load_state_dict``, ``torch.optim`` steps, ``module.half().float()``, ``reset_running_stats()`` --
+    and the package's own writers (``optim.Adam``, ``WeightEMA``, ``recalibrate_bn``, the train step, ``GraphedTrainStep``)
+    bump the epoch.  An in-place edit through ``.data`` (``p.data.mul_(2)``) moves neither address nor version and CANNOT
+    be seen: follow it with ``tactilesr_amd.invalidate_weight_packs()``."""
     _plan_fields = ("conv_impl",)
 
+    _plan_gen = 0        # moved by `_apply` (.half() / .float() / .to() of this module or of a parent)
+
     def _param_key(self):
-        return tuple(getattr(self, f) for f in self._plan_fields) + (_lib.param_epoch(),) + tuple(
-            (t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        key = [getattr(self, f) for f in self._plan_fields]
+        key.append(_lib.param_epoch())
+        for m in self.modules():         # one walk of the tree: every parameter and buffer, every BatchNorm eps, every generation
+            for t in m._parameters.values():
+                if t is not None:
+                    key.append(t.data_ptr())
+                    key.append(t._version)
+            for t in m._buffers.values():
+                if t is not None:
+                    key.append(t.data_ptr())
+                    key.append(t._version)
+            if isinstance(m, nn.BatchNorm2d):
+                key.append(m.eps)
+            else:
+                key.append(m.__dict__.get("_plan_gen", 0))
+        return tuple(key)
+
+    def _apply(self, fn, *args, **kwargs):
+        # .half() / .float() / .to(): `param.data = fn(param.data)` bumps no version, and the caching allocator may hand the
+        # new tensor the address the old one just released
+        out = super()._apply(fn, *args, **kwargs)
+        self._plan_gen += 1
+        return out
 
     def _get_plan(self):
         key = self._param_key()
