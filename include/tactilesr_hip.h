@@ -844,6 +844,65 @@ int tsr_taxel_noise_dev(const float* x, float* out, int B, int C, int H, int W, 
 int tsr_taxel_noise_bits(unsigned* out, int B, int blocks, const long long* ids, long long id_base, int tag,
                          unsigned long long seed, unsigned offset, void* stream);
 
+/* Contact readout (csrc/contact_readout.hip): where the contact is, how large, how oriented and how heavy, read out of a
+ * pressure image -- and, for a pair (output y, target t), how far the two contacts are apart -- from one launch.  The
+ * reference builds its targets from binarised contact masks (utility/raw_data_process.py:105-106 thresholds the depth at
+ * 0.5 min + 0.5 max; model/tPSFNet.py:87 calls the result the contact surface); mode 1 at threshold 0.5 is that rule.
+ * Per image, all arithmetic in double from the exact fp32 pixels v_p, p = (x, c) in row-major order:
+ *   tau   mode 0 ("abs"):   (double)(float)threshold
+ *         mode 1 ("range"): mn + threshold (mx - mn), mn / mx the image's own minimum / maximum, evaluated as a separate
+ *                           subtraction, product and sum (no fused contraction); y and t each use their own tau
+ *   m_p = [(double)v_p > tau]                                       the comparison is strict
+ *   u(x) = (x + 0.5) span_r / H - 0.5,  v(c) = (c + 0.5) span_c / W - 0.5     taxel-pitch units, independent of the grid:
+ *                                                                    with span = 4 taxel a's centre is at u = a (on the
+ *                                                                    100x100 grid pixel 12 + 25 a, the reference's centres)
+ * Record (TSR_CONTACT_REC = 16 floats), M0 = sum_p m_p v_p:
+ *   [0]  n = sum_p m_p                           [1]  area = n (span_r / H)(span_c / W)
+ *   [2]  mass M = gain M0                        [3]  total = gain sum_p v_p              [4]  peak = gain mx
+ *   [5], [6]   (u, v) of the first maximum in row-major order
+ *   [7], [8]   centroid (cu, cv) = sum_p m_p v_p (u, v) / M0
+ *   [9], [10], [11]   muu, mvv, muv = sum_p m_p v_p (u - cu)^2 / M0, ... (v - cv)^2 ..., ... (u - cu)(v - cv) ...
+ *   [12] theta = 0.5 atan2(2 muv, muu - mvv) in (-pi/2, pi/2]; exactly 0 when both arguments are 0; a value whose fp32
+ *        rounding would be -fl32(pi/2) is stored as +pi/2, the same axis
+ *   [13], [14]   sqrt(lambda+), sqrt(lambda-),  lambda+- = (muu + mvv)/2 +- sqrt(((muu - mvv)/2)^2 + muv^2), each clamped
+ *                at 0 before the root
+ *   [15] tau
+ *   With n = 0 or M0 <= 0 the entries 7..14 are NaN; 0..6 and 15 are still valid.
+ * The moments are summed about the peak pixel in integer pixel offsets (exact products) and moved to the centroid at the
+ * end: a one-pixel contact has moments and axes of exactly 0, never a negative root or a NaN.
+ * Pair (TSR_CONTACT_PAIR = 8 floats):
+ *   [0]  intersection count sum_p m^y_p m^t_p   [1]  union count n_y + n_t - [0]
+ *   [2]  IoU = [0] / [1]; 1 when the union is 0 [3]  Dice = 2 [0] / (n_y + n_t); 1 when both masks are empty
+ *   [4]  centroid distance sqrt((cu_y - cu_t)^2 + (cv_y - cv_t)^2); NaN when either contact is empty (has NaN geometry)
+ *   [5]  |M_y - M_t| / M_t; NaN when n_t = 0 or M_t <= 0
+ *   [6]  distance between the two peak positions
+ *   [7]  |theta_y - theta_t| folded into [0, pi/2] (d > pi/2 -> pi - d); NaN when either is NaN
+ * y (B,1,H,W) fp32 contiguous.  t optional, the same shape; NULL = one image per sample, rec_t and pair must then be
+ * NULL.  rec_y (B,16).  rec_t (B,16), optional when t is given.  pair (B,8), required when t is given.  y and t may be
+ * the same buffer.  Every stored value is rounded to fp32 once, at the store; H W <= 2^24 keeps the counts exact.
+ * One workgroup of 256 per image (pair), at most TSR_CONTACT_MAX_WGS of them walking the batch at a stride of the grid.
+ * Two passes: minimum, maximum, first maximum and a non-finite flag; then counts and moments, re-read from cache.  Thread k
+ * owns pixels 4j .. 4j+3 of the flat image for j = k, k + 256, ...; 16-byte loads when W % 4 == 0 and the base is 16-byte
+ * aligned, otherwise the same pixels one float at a time through the same arithmetic, with the same bits.  The map and the
+ * reduction order (shuffle tree per wave, waves in order) depend on (H, W) alone; no atomics and no host synchronisation:
+ * two launches give the same bits, and the launch can be captured in a HIP graph.
+ * Non-finite input: images are independent.  An image that holds a NaN or an Inf gets an all-NaN record; when it belongs
+ * to a pair, pair is all-NaN too and the clean partner keeps its own valid record.  Every other image keeps the bits of
+ * the clean run.  Bad input never causes an out-of-range access.
+ * Refusals (status 1, before any device call, nothing written): a NULL y or rec_y; B, H or W <= 0; H W > 2^24; mode outside
+ * 0..1; threshold NaN or Inf; mode 1 with threshold outside [0, 1); gain NaN or Inf; span_r or span_c <= 0, NaN or Inf;
+ * t NULL with rec_t or pair given; t given without pair; any output overlapping an input or another output. */
+#define TSR_CONTACT_REC 16
+#define TSR_CONTACT_PAIR 8
+#define TSR_CONTACT_MAX_WGS 2048
+int tsr_contact_readout(const float* y, const float* t, int B, int H, int W, int mode, double threshold, double gain,
+                        double span_r, double span_c, float* rec_y, float* rec_t, float* pair, void* stream);
+/* The same launch with the caller's grid cap (tsr_contact_readout is this with max_wgs = TSR_CONTACT_MAX_WGS).  The result
+ * does not depend on max_wgs, bit for bit.  Refusals: those above, and max_wgs < 1. */
+int tsr_contact_readout_wgs(const float* y, const float* t, int B, int H, int W, int mode, double threshold, double gain,
+                            double span_r, double span_c, float* rec_y, float* rec_t, float* pair, int max_wgs,
+                            void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * tPSFNet (model/tPSFNet.py): batched, one workgroup per sample (the reference loops over the
  * batch in python, :118-125).  size is fixed at 100x100 depth / 99x99 PSF / 4x4 taxels, as the

@@ -115,6 +115,8 @@ SIGNATURES = {
                             _P],
     "tsr_taxel_noise_dev": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _I, _F, _P, _L, _P, _P],
     "tsr_taxel_noise_bits": [_P, _I, _I, _P, _L, _I, ctypes.c_ulonglong, ctypes.c_uint, _P],
+    "tsr_contact_readout": [_P, _P, _I, _I, _I, _I, c_double, c_double, c_double, c_double, _P, _P, _P, _P],
+    "tsr_contact_readout_wgs": [_P, _P, _I, _I, _I, _I, c_double, c_double, c_double, c_double, _P, _P, _P, _I, _P],
     "tpsf_forward": [_P, _P, _P, _P, _P, _I, _P],
     "tpsf_backward": [_P, _P, _P, _P, _P, _P, _I, _P],
     "tpsf_backward_ex": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],

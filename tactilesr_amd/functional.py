@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import dataclasses as _dc
 import math as _math
+import typing as _typing
 
 import torch
 
@@ -1063,3 +1064,155 @@ def taxel_noise_bits(B: int, blocks: int, tag: int, seed: int = 0, offset: int =
     call("tsr_taxel_noise_bits", ptr(out), _I(B), _I(blocks), ptr(ids), _L(int(id_base)), _I(tag), ctypes.c_ulonglong(seed),
          ctypes.c_uint(offset), stream())
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Contact readout (tsr_contact_readout, csrc/contact_readout.hip): the geometry of the contact region of a pressure image
+# and the overlap / error metrics of a pair, from one launch.  A readout: not differentiable, no autograd graph.
+# ----------------------------------------------------------------------------------------------------------------------
+CONTACT_REC = 16                                                # TSR_CONTACT_REC of include/tactilesr_hip.h
+CONTACT_PAIR = 8                                                # TSR_CONTACT_PAIR
+CONTACT_MAX_WGS = 2048                                          # TSR_CONTACT_MAX_WGS
+CONTACT_MAX_PIXELS = 1 << 24                                    # counts stay exact in fp32
+CONTACT_MODES = {"abs": 0, "range": 1}
+
+
+class ContactReadout(_typing.NamedTuple):
+    """One contact per image, in taxel-pitch units (``u`` along rows, ``v`` along columns; with ``span = 4`` taxel ``a``'s
+    centre is at ``a``).  ``moments`` is ``(muu, mvv, muv)``; ``major`` / ``minor`` are the roots of the eigenvalues of
+    that matrix; ``raw`` is the (B,16) record of ``tsr_contact_readout`` the other fields are views of."""
+    count: torch.Tensor
+    area: torch.Tensor
+    mass: torch.Tensor
+    total: torch.Tensor
+    peak: torch.Tensor
+    peak_pos: torch.Tensor
+    centroid: torch.Tensor
+    moments: torch.Tensor
+    angle: torch.Tensor
+    major: torch.Tensor
+    minor: torch.Tensor
+    tau: torch.Tensor
+    raw: torch.Tensor
+
+
+class ContactMetrics(_typing.NamedTuple):
+    """The pair record of ``tsr_contact_readout``: ``raw`` is (B,8), the other fields are its columns."""
+    inter: torch.Tensor
+    union: torch.Tensor
+    iou: torch.Tensor
+    dice: torch.Tensor
+    centroid_dist: torch.Tensor
+    mass_rel_err: torch.Tensor
+    peak_dist: torch.Tensor
+    angle_diff: torch.Tensor
+    raw: torch.Tensor
+
+
+def _contact_readout_of(raw: torch.Tensor) -> ContactReadout:
+    return ContactReadout(raw[:, 0], raw[:, 1], raw[:, 2], raw[:, 3], raw[:, 4], raw[:, 5:7], raw[:, 7:9], raw[:, 9:12],
+                          raw[:, 12], raw[:, 13], raw[:, 14], raw[:, 15], raw)
+
+
+def _contact_metrics_of(raw: torch.Tensor) -> ContactMetrics:
+    return ContactMetrics(*(raw[:, i] for i in range(CONTACT_PAIR)), raw)
+
+
+def contact_readout_args(threshold=0.0, mode="abs", gain=1.0, span=(4.0, 4.0)):
+    """``(threshold, mode, gain, (span_r, span_c))`` as floats, a mode name and a pair, checked against what
+    ``tsr_contact_readout`` refuses; ``TactileSRHipError`` otherwise.  Host-only."""
+    if not isinstance(mode, str) or mode not in CONTACT_MODES:
+        raise TactileSRHipError(f"the contact threshold mode must be one of {sorted(CONTACT_MODES)}, got {mode!r}")
+    try:
+        thr, g = float(threshold), float(gain)
+        sp = (float(span), float(span)) if isinstance(span, (int, float)) else tuple(float(s) for s in span)
+    except (TypeError, ValueError) as e:
+        raise TactileSRHipError(f"contact readout: {e}") from None
+    if not _math.isfinite(thr):
+        raise TactileSRHipError(f"the contact threshold must be finite, got {thr}")
+    if mode == "range" and not 0.0 <= thr < 1.0:
+        raise TactileSRHipError(f"a \"range\" contact threshold is a fraction in [0, 1), got {thr}")
+    if not _math.isfinite(g):
+        raise TactileSRHipError(f"the contact gain must be finite, got {g}")
+    if len(sp) != 2 or not all(_math.isfinite(s) and s > 0 for s in sp):
+        raise TactileSRHipError(f"the contact span is one or two positive finite numbers, got {span!r}")
+    return thr, mode, g, sp
+
+
+def _contact_image(y: torch.Tensor, who: str) -> torch.Tensor:
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise TactileSRHipError(f"{who} needs ROCm tensors (no CPU fallback)")
+    if y.dtype != torch.float32:
+        raise TactileSRHipError(f"{who} needs fp32 images, got {y.dtype}")
+    if y.dim() == 3:
+        y = y.unsqueeze(1)
+    if y.dim() != 4 or y.shape[1] != 1 or y.shape[0] < 1 or not 1 <= y.shape[2] * y.shape[3] <= CONTACT_MAX_PIXELS:
+        raise TactileSRHipError(f"{who} needs (B,1,H,W) or (B,H,W) images with B >= 1 and 1 <= H W <= 2^24, got "
+                                f"{tuple(y.shape)}")
+    return y.detach().contiguous()
+
+
+def _contact_launch(y, t, args, rec_y, rec_t, pair, max_wgs=None):
+    thr, mode, gain, span = args
+    B, _, H, W = y.shape
+    a = [ptr(y), ptr(t), _I(B), _I(H), _I(W), _I(CONTACT_MODES[mode]), _D(thr), _D(gain), _D(span[0]), _D(span[1]),
+         ptr(rec_y), ptr(rec_t), ptr(pair)]
+    if max_wgs is None:
+        call("tsr_contact_readout", *a, stream())
+    else:
+        call("tsr_contact_readout_wgs", *a, _I(int(max_wgs)), stream())
+
+
+def contact_readout(y: torch.Tensor, threshold: float = 0.0, mode: str = "abs", gain: float = 1.0, span=(4.0, 4.0),
+                    max_wgs=None) -> ContactReadout:
+    """The contact of every image of ``y`` ((B,1,H,W) or (B,H,W), fp32, on the device) from one
+    ``tsr_contact_readout`` launch, no autograd: the pixels above the threshold -- ``mode="abs"``: ``v > threshold``;
+    ``mode="range"``: ``v > mn + threshold (mx - mn)`` of the image's own range, at 0.5 the reference's binarisation
+    (utility/raw_data_process.py:105-106) -- their count, area, mass (``gain`` times the masked sum), the image's total
+    and peak, the peak position, the intensity-weighted centroid, central second moments, orientation and axes.
+    ``span`` is the extent of the image in taxel pitches (rows, columns).  An image without contact has NaN geometry
+    (centroid, moments, angle, axes); an image with a NaN or Inf has an all-NaN record.  Nothing is read back."""
+    args = contact_readout_args(threshold, mode, gain, span)
+    y = _contact_image(y, "contact_readout")
+    if max_wgs is not None and int(max_wgs) < 1:
+        raise TactileSRHipError(f"contact_readout: max_wgs must be at least 1, got {max_wgs}")
+    raw = torch.empty(y.shape[0], CONTACT_REC, dtype=torch.float32, device=y.device)
+    _contact_launch(y, None, args, raw, None, None, max_wgs)
+    return _contact_readout_of(raw)
+
+
+def contact_metrics(y: torch.Tensor, t: torch.Tensor, threshold: float = 0.0, mode: str = "abs", gain: float = 1.0,
+                    span=(4.0, 4.0)):
+    """``(ContactMetrics, readout_y, readout_t)`` of an output ``y`` and a target ``t`` of the same shape from one
+    ``tsr_contact_readout`` launch: mask intersection, union, IoU and Dice, the centroid distance (pitch units), the
+    relative mass error ``|M_y - M_t| / M_t``, the peak distance and the orientation difference folded into [0, pi/2],
+    plus both images' own readouts.  Each image is thresholded against its own ``tau`` (``mode="range"``).  A value that
+    needs a contact that is not there is NaN.  No resampling: a target on another grid goes through ``prepare_target``."""
+    args = contact_readout_args(threshold, mode, gain, span)
+    y = _contact_image(y, "contact_metrics")
+    t = _contact_image(t, "contact_metrics")
+    if t.shape != y.shape or t.device != y.device:
+        raise TactileSRHipError(f"contact_metrics: the pair must share a shape and a device, got {tuple(y.shape)} on "
+                                f"{y.device} and {tuple(t.shape)} on {t.device}")
+    B = y.shape[0]
+    rec = torch.empty(2, B, CONTACT_REC, dtype=torch.float32, device=y.device)
+    pair = torch.empty(B, CONTACT_PAIR, dtype=torch.float32, device=y.device)
+    _contact_launch(y, t, args, rec[0], rec[1], pair)
+    return _contact_metrics_of(pair), _contact_readout_of(rec[0]), _contact_readout_of(rec[1])
+
+
+@torch.no_grad()
+def sr_readout(model, LR: torch.Tensor, **readout_kwargs):
+    """``(out, readout)``: the model's eval forward on ``LR`` and the ``contact_readout`` of its output, under
+    ``no_grad`` (the model's training flag is restored) -- the call a sensor loop makes.  ``readout_kwargs`` are those
+    of ``contact_readout`` and are checked before the forward runs."""
+    contact_readout_args(**{k: v for k, v in readout_kwargs.items() if k != "max_wgs"})
+    if not model.training:                                          # the sensor loop: no walk over the modules
+        out = model(LR)
+    else:
+        model.eval()
+        try:
+            out = model(LR)
+        finally:
+            model.train(True)
+    return out, contact_readout(out.float(), **readout_kwargs)

@@ -125,6 +125,50 @@ def degradation_loss_config(config):
     return w, gamma, ch, gain
 
 
+def contact_readout_config(config):
+    """The optional contact-readout keys, returned as ``(threshold, mode, gain, span)`` the way
+    ``functional.contact_metrics`` takes them:
+
+    * ``contact_threshold`` (default 0.0) -- the key the contact weight of ``pixel_loss_config`` already reads: the
+      contact is ``HR > contact_threshold`` on the prepared target, and the same rule is applied to the output;
+    * ``contact_threshold_mode`` (default ``"abs"``) -- ``"range"`` makes the threshold a fraction in [0, 1) of each
+      image's own range, 0.5 being the reference's binarisation (utility/raw_data_process.py:105-106);
+    * ``contact_span`` (default ``(4, 4)``) -- the extent of the image in taxel pitches, one number or (rows, columns);
+    * the gain is ``HR_scale_num``: masses come out in the dataset's units, before ``_prep`` divided the target.
+
+    A bad value raises ``TactileSRHipError`` here, before any launch."""
+    try:
+        gain = float(config.get("HR_scale_num", 1.0))
+    except (TypeError, ValueError) as e:
+        raise TactileSRHipError(f"HR_scale_num: {e}") from None
+    return Fh.contact_readout_args(config.get("contact_threshold", 0.0), config.get("contact_threshold_mode", "abs"),
+                                   gain, config.get("contact_span", (4, 4)))
+
+
+class _ContactSums:
+    """Whole-set sums of ``contact_iou``, ``contact_centroid_err`` and ``contact_mass_err`` for ``eval_func``: per value
+    ``sum_b w_b v_b`` and ``sum_b w_b`` over the samples whose value is not NaN and whose weight is not 0, in fp64 on the
+    device; one read-back at the end."""
+    COLS = (2, 4, 5)                                              # IoU, centroid distance, relative mass error
+
+    def __init__(self):
+        self.tot = None
+
+    def add(self, pair_raw, weight=None):
+        v = pair_raw[:, list(self.COLS)].double()
+        w = torch.ones(v.shape[0], dtype=torch.float64, device=v.device) if weight is None else weight.double()
+        keep = ~torch.isnan(v) & (w != 0)[:, None]
+        wk = torch.where(keep, w[:, None].expand_as(v), torch.zeros_like(v))
+        part = torch.stack([(torch.where(keep, v, torch.zeros_like(v)) * wk).sum(0), wk.sum(0)])
+        self.tot = part if self.tot is None else self.tot + part
+
+    def means(self):
+        if self.tot is None:
+            return (float("nan"),) * 3
+        num, den = self.tot.cpu().tolist()
+        return tuple(n / d if d > 0 else float("nan") for n, d in zip(num, den))
+
+
 def _degradation_gamma(deg, batch_gamma):
     """The gamma the launch takes: the batch's own, else the config scalar; refused when a non-zero weight has neither."""
     if batch_gamma is not None:
@@ -256,7 +300,7 @@ def train_one_iter(model, optimizer, batch, config, grad_sync=None, check_finite
 
 @torch.no_grad()
 def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=None, ema=None, taxel_noise=None,
-              noise_seed=0, degradation=False):
+              noise_seed=0, *, contact=False, degradation=False):
     """The reference's three averages (loss, SSIM, PSNR).  ``windowed_ssim=True`` appends a fourth: the windowed SSIM
     of ``functional.ssim`` with the config's ``ssim_window`` / ``ssim_sigma`` / ``ssim_data_range`` (``ssim_loss_config``),
     averaged the same way; the first three are unchanged.
@@ -284,11 +328,23 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
     ``sum_b w_b m_b / sum_b w_b`` over the whole set, from the per-sample values (``functional.pixel_loss_per_sample``,
     ``psnr_ssim``, ``ssim``) through ``functional.weighted_mean``: a sample with ``w_b = 0`` stays out even when its
     metric is NaN (its ``HR`` may hold anything), and a set whose weights sum to 0 returns NaN for these averages.  The
-    degradation score stays the plain mean over all samples.  Without weights the results are unchanged."""
+    degradation score stays the plain mean over all samples.  Without weights the results are unchanged.
+
+    ``contact=True`` (default ``False``: the returned tuple unchanged, bit for bit) appends three values after every
+    other one: ``contact_iou``, ``contact_centroid_err`` (taxel pitches) and ``contact_mass_err`` (relative), from one
+    ``functional.contact_metrics`` launch per batch on ``(out, HR)`` with the keys of ``contact_readout_config``.  They
+    are sample means over the whole set, ``sum_b v_b / #valid`` -- not means of batch means -- in which a sample whose
+    value is NaN (no contact on one side) is left out of that value; a value with no valid sample is NaN.  With weighted
+    batches they are ``sum_b w_b v_b / sum_b w_b`` over the valid samples with ``w_b != 0``.  It composes with
+    ``self_ensemble``, ``ema``, ``taxel_noise`` and ``degradation``.
+
+    ``contact`` and ``degradation`` are passed by keyword."""
     if ema is not None:
         with ema.applied():
             return eval_func(model, test_loader, config, windowed_ssim, self_ensemble, None, taxel_noise, noise_seed,
-                             degradation)
+                             contact=contact, degradation=degradation)
+    con = contact_readout_config(config) if contact else None
+    con_sums = _ContactSums() if contact else None
     deg = degradation_loss_config({**config, "degradation_loss_weight": 1.0}) if degradation else None
     tot_deg = 0.0
     noise = Fh.taxel_noise_spec(taxel_noise)
@@ -329,6 +385,8 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
             tot_ssim += float(ss.mean())
             if windowed_ssim:
                 tot_wssim += float(Fh.ssim(out, HR, data_range, window, sigma).mean())
+        if contact:
+            con_sums.add(Fh.contact_metrics(out.float(), HR, *con)[0].raw, sw)
         if degradation:
             gamma = _degradation_gamma(deg, _batch_gamma(batch, device))
             tot_deg += float(Fh.degradation_fwd_bwd(out, LR[:, deg[2]], gamma, deg[3], want_dy=False)[0].mean())
@@ -344,4 +402,6 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
             res += (tot_wssim / n,)
     if degradation:
         res += (tot_deg / n,)
+    if contact:
+        res += con_sums.means()
     return res
