@@ -147,7 +147,7 @@ class GradSink:
 
     def __init__(self, owner, named_params: Dict[str, torch.nn.Parameter], device, token=None, want=None):
         self.owner, self.device = owner, device
-        arena = getattr(owner, "arena", None)
+        arena = laid_out = getattr(owner, "arena", None)
         if arena is not None and any(n not in named_params or named_params[n].shape != arena.shapes[n]
                                      for n in arena.names):
             arena = owner.arena = None                                   # the module tree changed: lay out again
@@ -170,6 +170,10 @@ class GradSink:
         if sync is not None:
             sync.backward_started("first" if self.first else ("direct" if self.direct else
                                                               ("shared" if self.shared else "accum")), device)
+            if arena is None and laid_out is not None and sync.arena is laid_out:
+                # the layout was dropped above and this backward may not lay a new one out (shared): a GradSync still bound
+                # to the old arena would reduce the old names only -- unbound, finish() reduces the .grad tensors themselves
+                sync.arena = None
         if self.direct:
             arena.begin()
         self.out: Dict[str, torch.Tensor] = {}

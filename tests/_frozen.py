@@ -60,6 +60,12 @@ PATTERNS = {
 }
 
 
+# standalone blocks: (kind, the frozen parameters, whether the block input asks for a gradient)
+BLOCK_SUBSETS = [("msrb", ("conv_3_2.0.weight", "conv_3_2.0.bias"), False), ("msrb", ("conv_5_1.0.weight",), True),
+                 ("msrb", ("confusion.weight", "confusion.bias", "conv_3_1.1.weight"), False),
+                 ("res", ("conv1.weight", "conv1.bias"), False), ("res", ("conv2.weight",), True)]
+
+
 def production_order(plan, want):
     """The wanted parameter gradients in the order the plan's launches produce them: the gradient arena's layout."""
     return [n for r in plan for n in r.params if n in want]

@@ -18,6 +18,7 @@ from tactilesr_amd.train import tactileSR_train as TR
 from tactilesr_amd.train.checkpoint import model_param_init
 from tactilesr_amd.train.graph import GraphedTrainStep
 
+import _bucket_peer as BP
 import _frozen as FZ
 
 pytestmark = pytest.mark.gpu
@@ -191,23 +192,7 @@ def test_head_dgrad_is_head_bwds_data_gradient_bit_for_bit(cin, h_ctot, H, W, b1
 
 
 # ------------------------------------------------------------------------------------------------------- the Seqs flow
-class _ModeLog:
-    """Records which case every GradSink of a backward took (tactilesr_amd.ddp.GradSink's first / direct / accum / shared)."""
-
-    def __enter__(self):
-        self.modes = modes = []
-        self._orig = orig = ddp.GradSink
-
-        class Logged(orig):
-            def __init__(self, *a, **kw):
-                super().__init__(*a, **kw)
-                modes.append("first" if self.first else "direct" if self.direct else "shared" if self.shared else "accum")
-        ddp.GradSink = Logged
-        return self
-
-    def __exit__(self, *exc):
-        ddp.GradSink = self._orig
-        return False
+_ModeLog = BP.SinkLog          # records which case every GradSink of a backward took (`modes`); shared with the bucket tests
 
 
 def _seqs_flow(freeze, seed=77):
@@ -283,9 +268,7 @@ def test_seqs_flow_with_frozen_transplant_eager_clipped_and_graphed():
 
 
 # ------------------------------------------------------------------------------------------------- standalone blocks
-BLOCKS = [("msrb", ("conv_3_2.0.weight", "conv_3_2.0.bias"), False), ("msrb", ("conv_5_1.0.weight",), True),
-          ("msrb", ("confusion.weight", "confusion.bias", "conv_3_1.1.weight"), False),
-          ("res", ("conv1.weight", "conv1.bias"), False), ("res", ("conv2.weight",), True)]
+BLOCKS = FZ.BLOCK_SUBSETS
 
 
 @pytest.mark.parametrize("kind,frozen,x_grad", BLOCKS, ids=[f"{k}-{f[0]}-x{int(x)}" for k, f, x in BLOCKS])
