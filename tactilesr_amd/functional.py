@@ -293,9 +293,6 @@ def pixel_loss_per_sample(y: torch.Tensor, target: torch.Tensor, kind: str = "ms
     return (pix, dy, dt) if want_dt else (pix, dy)
 
 
-def _plain_mse(pixel_kind, fg_weight) -> bool:
-    return str(pixel_kind).lower() == "mse" and float(fg_weight) == 0
-
 
 # ----------------------------------------------------------------------------------------------------------------------
 # Degradation consistency (tsr_degrade_fwd_bwd, csrc/degrade_loss.hip): the image pooled onto the 4x4 taxels by the
@@ -440,6 +437,85 @@ def degradation_loss(y: torch.Tensor, z: torch.Tensor, gamma, gain: float = 1.0)
     return _DegradationLoss.apply(y.float(), z, gamma, gain)
 
 
+@_dc.dataclass(frozen=True)
+class SRLossOptions:
+    """The constants of the SR training loss under ``sr_loss_fwd_bwd``'s names and defaults; the tensors of a call
+    (``deg_z``, ``deg_gamma``, ``sample_weight``) travel beside it.  Hashable.  ``deg_gain`` is read only with a
+    non-zero ``deg_weight``."""
+    ssim_weight: float = 0.0
+    data_range: float = 1.0
+    window: int = 11
+    sigma: float = 1.5
+    K1: float = 0.01
+    K2: float = 0.03
+    pixel_kind: str = "mse"
+    pixel_param: _typing.Optional[float] = None
+    fg_weight: float = 0.0
+    fg_threshold: float = 0.0
+    deg_weight: float = 0.0
+    deg_gain: _typing.Optional[float] = 1.0
+    sample_weight_norm: str = "sum"
+
+    @property
+    def plain_mse(self) -> bool:
+        """The reference's criterion, nn.MSELoss: the pixel term is then the MSE launch."""
+        return str(self.pixel_kind).lower() == "mse" and float(self.fg_weight) == 0
+
+
+class SRLossTerms(_typing.NamedTuple):
+    """What one evaluation of the SR loss gives; ``None`` where a term is absent.  ``pixel`` is the pixel term (the
+    weighted one with weights), ``ssim`` and ``q`` the per-sample values of the SSIM and degradation terms, ``pix_b``,
+    ``scale`` and ``stats`` the per-sample pixel values and ``sample_scale``'s two results of a weighted batch.  ``dy``
+    is ``None`` in the autograd form."""
+    loss: torch.Tensor
+    dy: _typing.Optional[torch.Tensor]
+    pixel: torch.Tensor
+    ssim: _typing.Optional[torch.Tensor]
+    q: _typing.Optional[torch.Tensor]
+    pix_b: _typing.Optional[torch.Tensor]
+    scale: _typing.Optional[torch.Tensor]
+    stats: _typing.Optional[torch.Tensor]
+
+
+def _optional_terms(t: SRLossTerms) -> tuple:
+    """The tail of the variable-length returns of ``sr_loss_fwd_bwd(return_parts=True)`` and ``sr_loss``."""
+    return ((t.q,) if t.q is not None else ()) + ((t.pix_b, t.scale, t.stats) if t.scale is not None else ())
+
+
+def _sr_loss_launches(y, target, o: SRLossOptions, deg_z, deg_gamma, sample_weight, parts: bool = True) -> SRLossTerms:
+    """Every launch of the SR loss, in the order of ``sr_loss_fwd_bwd``'s docstring; ``loss`` and ``pixel`` are (1,)
+    tensors.  ``parts=False`` leaves out the one launch that only a report needs (the weighted pixel term beside an SSIM
+    term): ``pixel`` is then the loss before the degradation term."""
+    if not y.is_cuda or not target.is_cuda:
+        raise TactileSRHipError("sr_loss_fwd_bwd needs ROCm tensors (no CPU fallback)")
+    lam, lam_d = float(o.ssim_weight), float(o.deg_weight)
+    if lam_d != 0 and (deg_z is None or deg_gamma is None):
+        raise TactileSRHipError("sr_loss_fwd_bwd: a non-zero deg_weight needs deg_z and deg_gamma")
+    B = y.shape[0]
+    s = stats = pix_b = vals = q = None
+    if sample_weight is not None:
+        s, stats = sample_scale(_sample_vector(sample_weight, B, y.device, "sr_loss_fwd_bwd"), o.sample_weight_norm)
+        pix_b, dy = pixel_loss_per_sample(y, target, o.pixel_kind, o.pixel_param, o.fg_weight, o.fg_threshold, scale=s)
+    elif o.plain_mse:
+        pix, dy = mse_fwd_bwd(y, target)
+    else:
+        pix, dy = pixel_loss_fwd_bwd(y, target, o.pixel_kind, o.pixel_param, o.fg_weight, o.fg_threshold)
+    if lam != 0:
+        vals = _ssim_launch(y.contiguous(), target.detach().float().contiguous(), o.data_range, o.window, o.sigma, o.K1, o.K2,
+                            dy, -lam / B, 1, scale=s)
+    if lam_d != 0:
+        q = degradation_fwd_bwd(y, deg_z, deg_gamma, o.deg_gain, dy=dy, dy_scale=lam_d / B, accumulate=True)[0]
+    if s is None:
+        loss = pix if vals is None else pix + lam * (1.0 - vals.mean())
+    else:
+        loss = pix = weighted_mean(pix_b if vals is None else pix_b + lam * (1.0 - vals), s)
+        if vals is not None and parts:
+            pix = weighted_mean(pix_b, s)
+    if q is not None:
+        loss = loss + lam_d * q.mean()
+    return SRLossTerms(loss, dy, pix, vals, q, pix_b, s, stats)
+
+
 def sr_loss_fwd_bwd(y: torch.Tensor, target: torch.Tensor, ssim_weight: float = 0.0, data_range: float = 1.0,
                     window: int = 11, sigma: float = 1.5, K1: float = 0.01, K2: float = 0.03, return_parts: bool = False,
                     pixel_kind: str = "mse", pixel_param=None, fg_weight: float = 0.0, fg_threshold: float = 0.0,
@@ -464,98 +540,56 @@ def sr_loss_fwd_bwd(y: torch.Tensor, target: torch.Tensor, ssim_weight: float = 
     unchanged degradation launch, and the weighted means (``weighted_mean``).  ``return_parts`` reports the weighted
     pixel term ``(1/B) sum s_b pix_b`` as ``pixel`` and appends three more: the per-sample ``pix (B,)``, ``s (B,)`` and
     the ``stats (2,)`` of ``sample_scale``."""
-    if not y.is_cuda or not target.is_cuda:
-        raise TactileSRHipError("sr_loss_fwd_bwd needs ROCm tensors (no CPU fallback)")
-    deg = float(deg_weight) != 0
-    if deg and (deg_z is None or deg_gamma is None):
-        raise TactileSRHipError("sr_loss_fwd_bwd: a non-zero deg_weight needs deg_z and deg_gamma")
-    if sample_weight is not None:
-        norm = sample_weight_norm_arg(sample_weight_norm)
-        B = y.shape[0]
-        s, stats = sample_scale(_sample_vector(sample_weight, B, y.device, "sr_loss_fwd_bwd"), norm)
-        pix_b, dy = pixel_loss_per_sample(y, target, pixel_kind, pixel_param, fg_weight, fg_threshold, scale=s)
-        per_sample, vals, q = pix_b, None, None
-        if ssim_weight != 0:
-            t = target.detach().float().contiguous()
-            vals = _ssim_launch(y.contiguous(), t, data_range, window, sigma, K1, K2, dy, -float(ssim_weight) / B, 1,
-                                scale=s)
-            per_sample = pix_b + float(ssim_weight) * (1.0 - vals)
-        if deg:
-            q = degradation_fwd_bwd(y, deg_z, deg_gamma, deg_gain, dy=dy, dy_scale=float(deg_weight) / B,
-                                    accumulate=True)[0]
-        loss = weighted_mean(per_sample, s)
-        pix = weighted_mean(pix_b, s) if (return_parts and per_sample is not pix_b) else loss
-        if deg:
-            loss = loss + float(deg_weight) * q.mean()
-        if not return_parts:
-            return loss, dy
-        return (loss, dy, pix, vals) + ((q,) if deg else ()) + (pix_b, s, stats)
-    if _plain_mse(pixel_kind, fg_weight):
-        mse, dy = mse_fwd_bwd(y, target)
-    else:
-        mse, dy = pixel_loss_fwd_bwd(y, target, pixel_kind, pixel_param, fg_weight, fg_threshold)
-    loss, vals = mse, None
-    if ssim_weight != 0:
-        t = target.detach().float().contiguous()
-        vals = _ssim_launch(y.contiguous(), t, data_range, window, sigma, K1, K2, dy, -float(ssim_weight) / y.shape[0], 1)
-        loss = mse + float(ssim_weight) * (1.0 - vals.mean())
-    if not deg:
-        return (loss, dy, mse, vals) if return_parts else (loss, dy)
-    q = degradation_fwd_bwd(y, deg_z, deg_gamma, deg_gain, dy=dy, dy_scale=float(deg_weight) / y.shape[0],
-                            accumulate=True)[0]
-    loss = loss + float(deg_weight) * q.mean()
-    return (loss, dy, mse, vals, q) if return_parts else (loss, dy)
+    t = _sr_loss_launches(y, target, SRLossOptions(ssim_weight, data_range, window, sigma, K1, K2, pixel_kind, pixel_param,
+                                                   fg_weight, fg_threshold, deg_weight, deg_gain, sample_weight_norm),
+                          deg_z, deg_gamma, sample_weight, parts=return_parts)
+    return (t.loss, t.dy, t.pixel, t.ssim) + _optional_terms(t) if return_parts else (t.loss, t.dy)
 
 
 class _SRLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, y, target, ssim_weight, data_range, window, sigma, pixel_kind, pixel_param, fg_weight, fg_threshold,
-                deg_weight, deg_z, deg_gamma, deg_gain, sample_weight=None, sample_weight_norm="sum"):
-        parts = sr_loss_fwd_bwd(y, target, ssim_weight, data_range, window, sigma, return_parts=True,
-                                pixel_kind=pixel_kind, pixel_param=pixel_param, fg_weight=fg_weight,
-                                fg_threshold=fg_threshold, deg_weight=deg_weight, deg_z=deg_z, deg_gamma=deg_gamma,
-                                deg_gain=deg_gain, sample_weight=sample_weight, sample_weight_norm=sample_weight_norm)
-        loss, dy, mse, vals = parts[:4]
-        ctx.save_for_backward(dy)
-        mse0 = mse[0]
-        if sample_weight is not None:            # (..., [q,] pix_b, s, stats): everything but the loss is a report
-            rest = parts[4:]
-            ctx.mark_non_differentiable(mse0, *([vals] if vals is not None else []), *rest)
-            return (loss[0], mse0, vals) + tuple(rest)
-        if len(parts) == 5:
-            ctx.mark_non_differentiable(mse0, vals, parts[4]) if vals is not None else \
-                ctx.mark_non_differentiable(mse0, parts[4])
-            return loss[0], mse0, vals, parts[4]
-        ctx.mark_non_differentiable(mse0, vals)
-        return loss[0], mse0, vals
+    def forward(ctx, y, target, deg_z, deg_gamma, sample_weight, opts):
+        t = _sr_loss_launches(y, target, opts, deg_z, deg_gamma, sample_weight)
+        ctx.save_for_backward(t.dy)
+        t = t._replace(loss=t.loss[0], dy=None, pixel=t.pixel[0])
+        ctx.mark_non_differentiable(*(v for v in t[1:] if v is not None))      # everything but the loss is a report
+        return tuple(t)
 
     @staticmethod
     def backward(ctx, gout, *_gparts):
         (dy,) = ctx.saved_tensors
-        return (dy * gout,) + (None,) * 15
+        return dy * gout, None, None, None, None, None
+
+
+def sr_loss_terms(y: torch.Tensor, target: torch.Tensor, opts: SRLossOptions, deg_z=None, deg_gamma=None, sample_weight=None,
+                  *, autograd: bool) -> SRLossTerms:
+    """The SR loss of ``sr_loss_fwd_bwd`` under the options ``opts`` (any object with ``SRLossOptions``'s attributes), with
+    ``loss`` and ``pixel`` as scalars.  ``autograd=True``: ``loss`` carries the gradient to ``y`` (nothing else gets
+    one) and ``dy`` is ``None``; ``autograd=False``: outside autograd, ``dy`` is the gradient.  The launches are the
+    same in both forms."""
+    if autograd:
+        return SRLossTerms(*_SRLoss.apply(y.float(), target, None if deg_z is None else deg_z.detach(), deg_gamma,
+                                          None if sample_weight is None else sample_weight.detach(), opts))
+    t = _sr_loss_launches(y.float(), target, opts, deg_z, deg_gamma, sample_weight)
+    return t._replace(loss=t.loss[0], pixel=t.pixel[0])
 
 
 def sr_loss(y: torch.Tensor, target: torch.Tensor, ssim_weight: float, data_range: float = 1.0, window: int = 11,
             sigma: float = 1.5, pixel_kind: str = "mse", pixel_param=None, fg_weight: float = 0.0,
             fg_threshold: float = 0.0, sample_weight=None, sample_weight_norm: str = "sum", deg_weight: float = 0.0,
             deg_z=None, deg_gamma=None, deg_gain: float = 1.0):
-    """The autograd form of ``sr_loss_fwd_bwd`` for a non-zero ``ssim_weight`` or ``deg_weight``:
+    """The autograd form of ``sr_loss_fwd_bwd``, a thin adapter over ``sr_loss_terms``:
     ``(loss, pixel term, per-sample ssim)`` and, with a non-zero ``deg_weight``, the per-sample ``q`` as a fourth
     (``ssim`` is then ``None`` when ``ssim_weight == 0``); only ``loss`` carries a gradient (to ``y`` -- the taxels
     ``deg_z`` get none here: ``degradation_loss`` is the form that differentiates them).  With ``sample_weight`` (any
     ``ssim_weight`` and ``deg_weight``, zero included) the weighted loss of ``sr_loss_fwd_bwd``; the tuple then ends
     with the per-sample ``pix (B,)``, the scale ``s (B,)`` and ``stats (2,)``, and its pixel term is the weighted one."""
-    if not y.is_cuda:
-        raise TactileSRHipError("sr_loss needs ROCm tensors (no CPU fallback)")
-    if float(deg_weight) != 0 and deg_z is None:
-        raise TactileSRHipError("sr_loss: a non-zero deg_weight needs deg_z and deg_gamma")
-    if sample_weight is not None:
-        return _SRLoss.apply(y.float(), target, float(ssim_weight), data_range, window, sigma, pixel_kind, pixel_param,
-                             fg_weight, fg_threshold, float(deg_weight), None if deg_z is None else deg_z.detach(),
-                             deg_gamma, float(deg_gain), sample_weight.detach(), sample_weight_norm_arg(sample_weight_norm))
-    return _SRLoss.apply(y.float(), target, float(ssim_weight), data_range, window, sigma, pixel_kind, pixel_param,
-                         fg_weight, fg_threshold, float(deg_weight), None if deg_z is None else deg_z.detach(), deg_gamma,
-                         float(deg_gain), None, "sum")
+    t = sr_loss_terms(y, target, SRLossOptions(ssim_weight, data_range, window, sigma, pixel_kind=pixel_kind,
+                                               pixel_param=pixel_param, fg_weight=fg_weight, fg_threshold=fg_threshold,
+                                               deg_weight=deg_weight, deg_gain=deg_gain,
+                                               sample_weight_norm=sample_weight_norm),
+                      deg_z, deg_gamma, sample_weight, autograd=True)
+    return (t.loss, t.pixel, t.ssim) + _optional_terms(t)
 
 
 def psnr_ssim(a: torch.Tensor, b: torch.Tensor, maxValue: float, reference_quirk: bool = True,

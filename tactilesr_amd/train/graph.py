@@ -20,11 +20,10 @@ Opt-in; the plain ``train_one_iter`` path is untouched.
 * Recapture: when ``train_impl``, the parameter / buffer / optimizer-state / gradient-arena addresses, the set of
   parameters that require grad (the captured backward holds only the launches a trainable parameter depends on), the set
   of BatchNorm layers in eval mode (``hold_bn_statistics``: their statistics launches are not in the capture), the loss
-  config (the optional ``ssim_loss_weight`` / ``ssim_window`` / ``ssim_sigma`` / ``ssim_data_range`` and ``pixel_loss`` /
-  ``pixel_loss_param`` / ``contact_loss_weight`` / ``contact_threshold`` and ``degradation_loss_weight`` /
-  ``degradation_gamma`` / ``degradation_channel`` / ``degradation_gain`` included: the captured loss is
-  ``functional.sr_loss_fwd_bwd``, the MSE or the configured pixel launch plus, for a non-zero weight, the SSIM launch
-  and, for a non-zero degradation weight, the degradation launch on a channel slice of the static ``LR``),
+  config (one ``SRLossSpec``, parsed from the optional ``ssim_*``, ``pixel_loss*`` / ``contact_*``, ``degradation_*`` and
+  ``sample_weight_norm`` keys: the captured loss and the returned dict are ``sr_step_loss``'s, the function
+  ``train_cal_loss`` itself calls -- here outside autograd, on the static buffers, the z-taxels a channel slice of the
+  static ``LR`` -- so the launches are those of ``functional.sr_loss_fwd_bwd`` in both steps),
   the optimizer's baked constants (``betas``, ``eps``, ``weight_decay``) or ``clip_grad_norm`` change, the graph is dropped and the next ``warmup`` calls run eagerly again before a new capture.  ``captures`` counts the captures.
 * The returned ``total_loss`` is the graph's static OUTPUT BUFFER (like ``GraphedForward``): the next call overwrites
   it, so clone it to keep it.  It carries no autograd graph.
@@ -67,13 +66,10 @@ from __future__ import annotations
 import torch
 
 from .. import _lib
-from .. import functional as Fh
 from .. import optim as opt_mod
 from .._lib import TactileSRHipError
 from ..ddp import note_forward
-from .tactileSR_train import (_batch_gamma, _batch_weight, _degradation_gamma, _prep, degradation_loss_config,
-                              pixel_is_plain_mse, pixel_loss_config, sample_weight_config, ssim_loss_config,
-                              train_one_iter)
+from .tactileSR_train import SRLossSpec, _batch_gamma, _batch_weight, _degradation_gamma, _prep, sr_step_loss, train_one_iter
 
 _CONFIG_KEYS = ("HR_scale_num", "scale_factor", "seqsCnt", "axisCnt")      # what the captured train_cal_loss bakes in
 
@@ -120,8 +116,7 @@ class GraphedTrainStep:
                        for g in opt.param_groups)
         return (m.train_impl, id(arena), arena.flat.data_ptr() if arena is not None else 0,
                 tuple(t.data_ptr() for t in m.parameters()), tuple(b.data_ptr() for b in m.buffers()), groups,
-                tuple(self.config[k] for k in _CONFIG_KEYS), ssim_loss_config(self.config), pixel_loss_config(self.config),
-                degradation_loss_config(self.config), sample_weight_config(self.config), self.clip_grad_norm,
+                tuple(self.config[k] for k in _CONFIG_KEYS), SRLossSpec.from_config(self.config), self.clip_grad_norm,
                 (id(self.ema), self.ema._flat.data_ptr(), self.ema.buffers) if self.ema is not None else None,
                 tuple(p.requires_grad for p in m.parameters()),      # the captured backward holds the trainable set's launches
                 tuple(mod.training for mod in m.modules() if isinstance(mod, torch.nn.BatchNorm2d)))      # and each BatchNorm's mode
@@ -160,12 +155,10 @@ class GraphedTrainStep:
     def _capture(self, LR, HR, gamma=None, weight=None) -> None:
         m, opt = self.model, self.optimizer
         dev = next(m.parameters()).device
-        pixel = pixel_loss_config(self.config)     # refuses a bad key before anything is captured
-        deg = degradation_loss_config(self.config)
+        spec = SRLossSpec.from_config(self.config)      # refuses a bad key before anything is captured
         if gamma is not None:
             self._G = torch.empty(gamma.shape, dtype=torch.float32, device=dev)
-        deg_gamma = _degradation_gamma(deg, self._G) if deg[0] != 0 else None
-        norm = sample_weight_config(self.config)
+        deg_gamma = _degradation_gamma(spec, self._G)
         if weight is not None:
             self._SW = torch.empty(weight.shape, dtype=torch.float32, device=dev)
         self._LR = torch.empty(LR.shape, dtype=LR.dtype, device=dev)
@@ -196,32 +189,8 @@ class GraphedTrainStep:
             named = [(n, p) for n, p in m.named_parameters() if p.requires_grad]
             if named:
                 note_forward(eng, ctx)
-            ssim_w, window, sigma, data_range = ssim_loss_config(self.config)
-            kind, param, fg_weight, fg_threshold = pixel
-            if weight is not None:               # train_cal_loss's weighted branch, on the static weight buffer
-                res = Fh.sr_loss_fwd_bwd(out.float(), HR, ssim_w, data_range, window, sigma, return_parts=True,
-                                         pixel_kind=kind, pixel_param=param, fg_weight=fg_weight,
-                                         fg_threshold=fg_threshold, deg_weight=deg[0],
-                                         deg_z=LR[:, deg[2]] if deg[0] != 0 else None, deg_gamma=deg_gamma,
-                                         deg_gain=deg[3] or 1.0, sample_weight=self._SW, sample_weight_norm=norm)
-                loss, dy, pix, vals = res[:4]
-                labeled = res[-1][0] / LR.shape[0]
-                w_ssim = Fh.weighted_mean(vals, res[-2])[0] if vals is not None else None
-                if deg[0] != 0:
-                    deg_mean = res[4].mean()
-            elif deg[0] == 0:
-                loss, dy, pix, vals = Fh.sr_loss_fwd_bwd(out.float(), HR, ssim_w, data_range, window, sigma,
-                                                         return_parts=True, pixel_kind=kind, pixel_param=param,
-                                                         fg_weight=fg_weight, fg_threshold=fg_threshold)
-            else:                                # the z-taxels are a slice of the static LR, read in place
-                loss, dy, pix, vals, q = Fh.sr_loss_fwd_bwd(out.float(), HR, ssim_w, data_range, window, sigma,
-                                                            return_parts=True, pixel_kind=kind, pixel_param=param,
-                                                            fg_weight=fg_weight, fg_threshold=fg_threshold,
-                                                            deg_weight=deg[0], deg_z=LR[:, deg[2]], deg_gamma=deg_gamma,
-                                                            deg_gain=deg[3])
-                deg_mean = q.mean()
-            # weight 0: the pixel launch alone; the plain MSE: mse_fwd_bwd
-            ssim_mean = vals.mean() if vals is not None and weight is None else None
+            # train_cal_loss's loss and loss_dict, on the static buffers (the z-taxels are a slice of the static LR)
+            _, dy, out_dict = sr_step_loss(spec, out, LR, HR, deg_gamma, self._SW, autograd=False)
             opt.zero_grad()
             grads = eng.backward(ctx, dy)
             del ctx
@@ -236,22 +205,6 @@ class GraphedTrainStep:
             if self.ema is not None:
                 ema_table = self.ema._captured_update(self._ema_omd)
         # the launches (and the norm launch) hold the Adam chunk tables the graph reads: keep them alive with it
-        out_dict = {"total_loss": loss[0]}
-        pix_key = "mse_loss" if pixel_is_plain_mse(pixel) else "pixel_loss"
-        if weight is not None:                   # train_cal_loss's loss_dict of a weighted batch
-            out_dict.update({pix_key: pix[0], "labeled_weight": labeled})
-            if vals is not None:
-                out_dict["ssim"] = w_ssim
-            if deg[0] != 0:
-                out_dict["degradation_loss"] = deg_mean
-        elif deg[0] != 0:                        # train_cal_loss's loss_dict with a degradation term
-            out_dict.update({pix_key: pix[0], "degradation_loss": deg_mean})
-            if vals is not None:
-                out_dict["ssim"] = ssim_mean
-        elif vals is not None:                   # with an SSIM term
-            out_dict.update({pix_key: pix[0], "ssim": ssim_mean})
-        elif pix_key == "pixel_loss":            # and with a configured pixel criterion alone
-            out_dict["pixel_loss"] = loss[0]
         self.graph, self._out, self._launches = graph, out_dict, launches
         self._norm_table = norm_table if clip else None
         self._ema_table = ema_table if self.ema is not None else None      # kept alive with the graph

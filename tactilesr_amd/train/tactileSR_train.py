@@ -10,7 +10,9 @@ path needs from it are the three functions below with the same argument meaning:
 """
 from __future__ import annotations
 
+import dataclasses
 import math
+import typing
 
 import torch
 
@@ -169,19 +171,78 @@ class _ContactSums:
         return tuple(n / d if d > 0 else float("nan") for n, d in zip(num, den))
 
 
-def _degradation_gamma(deg, batch_gamma):
-    """The gamma the launch takes: the batch's own, else the config scalar; refused when a non-zero weight has neither."""
-    if batch_gamma is not None:
-        return batch_gamma
-    if deg[1] is None:
-        raise TactileSRHipError("degradation_loss_weight is non-zero but there is no degradation_gamma key and the batch "
-                                "carries no gamma")
-    return deg[1]
-
-
 def pixel_is_plain_mse(pixel) -> bool:
     """Whether a ``pixel_loss_config`` result is the reference's criterion: the step then issues the MSE launch."""
     return pixel[0] == "mse" and pixel[2] == 0
+
+
+@dataclasses.dataclass(frozen=True)
+class SRLossSpec(Fh.SRLossOptions):
+    """The loss of the SR train step as the config states it, parsed once: ``functional.SRLossOptions`` (what the loss
+    launches read) plus where the degradation term finds its inputs -- ``deg_gamma``, the config's scalar (``None``: the
+    batch carries one), and ``deg_channel``, the channel of the prepared ``LR`` that holds the z-taxels.  With the
+    degradation term off, ``deg_gamma``, ``deg_channel`` and ``deg_gain`` are ``None`` (``degradation_loss_config``).
+    Hashable: ``GraphedTrainStep`` keys its capture on it."""
+    deg_gamma: typing.Optional[float] = None
+    deg_channel: typing.Optional[int] = None
+
+    @classmethod
+    def from_config(cls, config) -> "SRLossSpec":
+        """From ``ssim_loss_config``, ``pixel_loss_config``, ``degradation_loss_config`` and ``sample_weight_config``: a
+        value one of them refuses raises its ``TactileSRHipError`` here, before any launch."""
+        ssim_weight, window, sigma, data_range = ssim_loss_config(config)
+        pixel_kind, pixel_param, fg_weight, fg_threshold = pixel_loss_config(config)
+        deg_weight, deg_gamma, deg_channel, deg_gain = degradation_loss_config(config)
+        return cls(ssim_weight=ssim_weight, window=window, sigma=sigma, data_range=data_range, pixel_kind=pixel_kind,
+                   pixel_param=pixel_param, fg_weight=fg_weight, fg_threshold=fg_threshold, deg_weight=deg_weight,
+                   deg_gamma=deg_gamma, deg_channel=deg_channel, deg_gain=deg_gain,
+                   sample_weight_norm=sample_weight_config(config))
+
+
+def _degradation_gamma(spec, batch_gamma):
+    """The gamma the degradation launch takes: the batch's own, else the config scalar; ``None`` with the term off;
+    refused when a non-zero weight has neither.  Both steps call it before the forward, so the refusal precedes every
+    launch."""
+    if spec.deg_weight == 0:
+        return None
+    if batch_gamma is not None:
+        return batch_gamma
+    if spec.deg_gamma is None:
+        raise TactileSRHipError("degradation_loss_weight is non-zero but there is no degradation_gamma key and the batch "
+                                "carries no gamma")
+    return spec.deg_gamma
+
+
+def sr_loss_report(spec, terms):
+    """The report dict of a train step from the ``functional.SRLossTerms`` of its loss -- the one rule of the eager and
+    the graph-captured step.  ``total_loss`` always; the pixel term under ``mse_loss`` (the plain MSE) or ``pixel_loss``
+    (any other pixel setting), unless the loss is the plain MSE with no other term and no weights; a configured criterion
+    alone reports the loss tensor itself as ``pixel_loss``.  With an SSIM term ``ssim``, the mean of the per-sample values
+    -- with weights the weighted mean ``(1/B) sum_b s_b ssim_b``, one more ``functional.weighted_mean`` launch; with a
+    degradation term ``degradation_loss`` = ``mean_b q_b``; with weights ``labeled_weight``, the sum of the valid
+    weights / B."""
+    d = {"total_loss": terms.loss}
+    alone = terms.ssim is None and terms.q is None and terms.scale is None
+    if not (alone and spec.plain_mse):
+        d["mse_loss" if spec.plain_mse else "pixel_loss"] = terms.loss if alone else terms.pixel
+    if terms.scale is not None:
+        d["labeled_weight"] = terms.stats[0] / terms.scale.shape[0]
+    if terms.ssim is not None:
+        d["ssim"] = terms.ssim.mean() if terms.scale is None else Fh.weighted_mean(terms.ssim, terms.scale)[0]
+    if terms.q is not None:
+        d["degradation_loss"] = terms.q.mean()
+    return d
+
+
+def sr_step_loss(spec, out, LR, HR, gamma, weight, *, autograd):
+    """``(loss, dy or None, loss_dict)`` of one train step from the model's output ``out`` on the prepared ``LR`` / ``HR``:
+    the loss of ``spec`` through ``functional.sr_loss_terms`` -- through autograd for the eager step (``dy`` is ``None``),
+    outside it for the graph capture (``dy`` is the gradient the engine's backward takes) -- and ``sr_loss_report``'s dict.
+    ``gamma`` is ``_degradation_gamma``'s result, ``weight`` the (B,) supervision weights or ``None``.  The z-taxels are
+    ``LR[:, spec.deg_channel]``, detached and read in place."""
+    deg_z = LR.detach()[:, spec.deg_channel] if spec.deg_weight != 0 else None
+    terms = Fh.sr_loss_terms(out, HR, spec, deg_z, gamma, weight, autograd=autograd)
+    return terms.loss, terms.dy, sr_loss_report(spec, terms)
 
 
 def train_cal_loss(model, batch, config):
@@ -201,46 +262,19 @@ def train_cal_loss(model, batch, config):
     of a sample with ``w_b = 0`` is never read by the loss (it may hold anything).  The dict then holds the weighted
     pixel term ``(1/B) sum_b s_b pix_b`` under its usual key, the weighted ``ssim`` ``(1/B) sum_b s_b ssim_b`` with an
     SSIM term, ``labeled_weight`` (the sum of the valid weights / B) and ``degradation_loss`` with that term; the plain
-    MSE setting runs the per-sample launch with kind ``"mse"``."""
+    MSE setting runs the per-sample launch with kind ``"mse"``.
+
+    Every setting takes one path: the config is parsed once into an ``SRLossSpec``, and ``sr_step_loss`` -- which the
+    capture of ``GraphedTrainStep`` calls too -- issues the launches of ``functional.sr_loss_fwd_bwd`` through one
+    autograd function and builds the dict by the rule of ``sr_loss_report``.  The configured ``degradation_gain`` reaches
+    the launch as parsed whatever the batch form (0.0 means 0)."""
     device = next(model.parameters()).device
-    pixel = pixel_loss_config(config)
-    deg = degradation_loss_config(config)
-    sw = _batch_weight(batch, device)
-    norm = sample_weight_config(config) if sw is not None else None
-    gamma = _degradation_gamma(deg, _batch_gamma(batch, device)) if deg[0] != 0 else None
+    spec = SRLossSpec.from_config(config)
+    weight = _batch_weight(batch, device)
+    gamma = _degradation_gamma(spec, _batch_gamma(batch, device) if spec.deg_weight != 0 else None)   # read with the term on
     LR, HR = _prep(batch, config, device)
-    out = model(LR)
-    weight, window, sigma, data_range = ssim_loss_config(config)
-    plain = pixel_is_plain_mse(pixel)
-    if sw is not None:
-        res = Fh.sr_loss(out, HR, weight, data_range, window, sigma, *pixel, deg_weight=deg[0],
-                         deg_z=LR.detach()[:, deg[2]] if deg[0] != 0 else None, deg_gamma=gamma, deg_gain=deg[3] or 1.0,
-                         sample_weight=sw, sample_weight_norm=norm)
-        loss, pix, vals = res[:3]
-        s, stats = res[-2], res[-1]
-        d = {"total_loss": loss, "mse_loss" if plain else "pixel_loss": pix,
-             "labeled_weight": stats[0] / LR.shape[0]}
-        if vals is not None:
-            d["ssim"] = Fh.weighted_mean(vals, s)[0]
-        if deg[0] != 0:
-            d["degradation_loss"] = res[3].mean()
-        return loss, d
-    if deg[0] != 0:
-        res = Fh.sr_loss(out, HR, weight, data_range, window, sigma, *pixel, deg_weight=deg[0],
-                         deg_z=LR.detach()[:, deg[2]], deg_gamma=gamma, deg_gain=deg[3])
-        loss, pix, vals, q = res
-        d = {"total_loss": loss, "mse_loss" if plain else "pixel_loss": pix, "degradation_loss": q.mean()}
-        if vals is not None:
-            d["ssim"] = vals.mean()
-        return loss, d
-    if weight == 0:
-        if plain:
-            loss = Fh.mse_loss(out, HR)
-            return loss, {"total_loss": loss}
-        loss = Fh.pixel_loss(out, HR, *pixel)
-        return loss, {"total_loss": loss, "pixel_loss": loss}
-    loss, pix, vals = Fh.sr_loss(out, HR, weight, data_range, window, sigma, *pixel)
-    return loss, {"total_loss": loss, "mse_loss" if plain else "pixel_loss": pix, "ssim": vals.mean()}
+    loss, _, loss_dict = sr_step_loss(spec, model(LR), LR, HR, gamma, weight, autograd=True)
+    return loss, loss_dict
 
 
 def fused_clip_applies(model, optimizer) -> bool:
@@ -345,7 +379,8 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
                              contact=contact, degradation=degradation)
     con = contact_readout_config(config) if contact else None
     con_sums = _ContactSums() if contact else None
-    deg = degradation_loss_config({**config, "degradation_loss_weight": 1.0}) if degradation else None
+    # the SSIM window and, for the degradation score (read whatever the configured weight), gamma / channel / gain
+    spec = SRLossSpec.from_config({**config, "degradation_loss_weight": 1.0} if degradation else config)
     tot_deg = 0.0
     noise = Fh.taxel_noise_spec(taxel_noise)
     seen = 0
@@ -353,8 +388,8 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
     model.eval()
     tot_loss = tot_ssim = tot_psnr = tot_wssim = 0.0
     n = 0
-    _, window, sigma, data_range = ssim_loss_config(config)
-    weighted = None              # whether the set's batches carry weights: all of them or none
+    window, sigma, data_range = spec.window, spec.sigma, spec.data_range
+    weighted = None             # whether the set's batches carry weights: all of them or none
     tot_w = 0.0
     for batch in test_loader:
         LR, HR = _prep(batch, config, device)
@@ -388,8 +423,8 @@ def eval_func(model, test_loader, config, windowed_ssim=False, self_ensemble=Non
         if contact:
             con_sums.add(Fh.contact_metrics(out.float(), HR, *con)[0].raw, sw)
         if degradation:
-            gamma = _degradation_gamma(deg, _batch_gamma(batch, device))
-            tot_deg += float(Fh.degradation_fwd_bwd(out, LR[:, deg[2]], gamma, deg[3], want_dy=False)[0].mean())
+            gamma = _degradation_gamma(spec, _batch_gamma(batch, device))
+            tot_deg += float(Fh.degradation_fwd_bwd(out, LR[:, spec.deg_channel], gamma, spec.deg_gain, want_dy=False)[0].mean())
         n += 1
     if weighted:
         avg = (lambda v: v / tot_w) if tot_w > 0 else (lambda v: float("nan"))

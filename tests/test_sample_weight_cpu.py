@@ -243,7 +243,8 @@ def test_sample_weight_config_and_the_batch_forms():
         with pytest.raises(ERR):
             TR.train_cal_loss(Spy(), batch, c)
     assert not ran
-    assert "sample_weight_config(self.config)" in inspect.getsource(GraphedTrainStep._key)     # the norm is in the key
+    assert "SRLossSpec.from_config(self.config)" in inspect.getsource(GraphedTrainStep._key)   # the norm is in the key
+    assert TR.SRLossSpec.from_config(dict(conf, sample_weight_norm="batch")) != TR.SRLossSpec.from_config(conf)
 
 
 def test_eval_func_on_a_stub_with_and_without_weights():
